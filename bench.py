@@ -25,7 +25,14 @@ descriptors back on the host, PCIe both ways -- timed the same way (exactly --st
 synchronize, median of the repeats) through the library's streaming pipeline (imf_pipeline_*: csrc/pipeline.hip).
 
   python bench.py [--gpus N --steps K --warmup W]        one JSON line on rank 0
+  python bench.py --full [...]                           + every other measurement (see below)
 With --gpus N > 1 and no torchrun environment the script launches its own N ranks.
+
+A plain run does only what the headline needs: set up, warm up (W steps + the clock settle + the --mode auto probe),
+time ONE region of exactly K steps, write the last step's outputs if --dump-outputs DIR is given, print the line.
+--full adds what the headline does not need: nine repeats of the timed region, the traced steps of the live roofline,
+host_span, the sharded-pipeline leg, the single-fragment / batch / e2e / graph legs, the other two arithmetics and the
+CPU baseline, with the full record written to bench_full.json.
 """
 import argparse
 import json
@@ -462,7 +469,7 @@ class Workload:
         """Round 1's path: geometry stream + one count readback + native executor."""
         with torch.cuda.stream(self.stream):
             fut = self._geo(self.xyz, self.voxel, self.dev, inputs_ready=True, item_starts=self.item_starts)
-            st, _ = self._sp(None, self.voxel, self.dev, geometry=fut)
+            st, self.last_inds = self._sp(None, self.voxel, self.dev, geometry=fut)
             self.last_st = st
             return self.model(st, self.img).F
 
@@ -538,6 +545,26 @@ def timed(fn, steps, sync):
 def median(vals):
     v = sorted(vals)
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+PROBE_STEPS = 100             # longest timed region of one --mode auto probe
+DUMP_BYTES = 63_000_000       # what --dump-outputs writes in all, .npy headers included (limit: 64 MB)
+
+
+def dump_outputs(dirname, F, xyz_down):
+    """What a caller of the timed path receives from one step -- descriptors [M,32] float32 and the voxel representatives
+    xyz_down [M,3] float64, row i of one describing row i of the other -- as <dirname>/<name>.npy.  A larger output is
+    cut to a fixed seeded sample of rows, the same rows in both, whose indices go to rows.npy."""
+    arrays = {"descriptors": F.float().cpu().numpy(), "xyz_down": xyz_down.double().cpu().numpy()}
+    m = arrays["descriptors"].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values()) + 8
+    if m * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(m, DUMP_BYTES // row_bytes, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def host_span_leg(model, dev, args, barrier, sync, pts, imgs, voxel, f32_valued=False, batch=None):
@@ -852,26 +879,38 @@ def main():
                          "are timed after the clocks have settled and the fastest runs the timed region "
                          "(config.capacity_mode.picked says which, probe_ms_per_step has all of them); exact: count readback + "
                          "native executor")
-    ap.add_argument("--repeats", type=int, default=9,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is repeated this many times; "
-                         "ms_per_step / value are the MEDIAN repeat, min and max are reported beside it")
+                         "ms_per_step / value are the MEDIAN repeat, min and max are reported beside it (default 1; "
+                         "9 with --full)")
     ap.add_argument("--settle-ms", type=float, default=600.0,
                     help="untimed steps run for at least this long before the first timed region (clock / power settle)")
     ap.add_argument("--trace-steps", type=int, default=3,
-                    help="steps AFTER the timed regions that carry HIP events around every convolution (live roofline)")
+                    help="steps AFTER the timed regions that carry HIP events around every convolution (live roofline; --full)")
     ap.add_argument("--arith", default=None, choices=tuple(ARITH),
                     help="arithmetic of the convolutions for the headline (`value`): bf16x3 (default: fp32 operands split exactly "
-                         "into three bf16 parts), f16x2 (the 22-bit FAST mode), f32 (fp32 MFMA).  The other two are measured "
-                         "too and reported with their own roofline under `arithmetics` (N = 1)")
+                         "into three bf16 parts), f16x2 (the 22-bit FAST mode), f32 (fp32 MFMA).  With --full the other two are "
+                         "measured too and reported with their own roofline under `arithmetics` (N = 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the single-fragment / batch / fp32-MFMA / graph legs")
     ap.add_argument("--no-host-span", action="store_true", help="skip the host-array stream leg (profiling runs)")
     ap.add_argument("--no-sharded", action="store_true", help="skip the sharded-pipeline + gather leg")
     ap.add_argument("--sharded-per-rank", type=int, default=96, help="fragments per rank of the sharded-pipeline leg")
     ap.add_argument("--sharded-region-s", type=float, default=1.2, help="minimum length of one timed region of that leg")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_full.json"),
-                    help="where the FULL record goes (every leg, note and per-kernel table); stdout carries only the compact line")
+    ap.add_argument("--full-out", default=None,
+                    help="where the FULL record goes (every leg, note and per-kernel table); stdout carries only the compact line "
+                         "(default with --full: bench_full.json in the repository root; a plain run writes it only when given)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: repeats, live roofline, host_span, sharded-pipeline, extra legs, other "
+                         "arithmetics, CPU baseline (the --no-* options above switch single ones off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (descriptors float32 [M,32], "
+                         "xyz_down float64 [M,3]) as DIR/<name>.npy -- a seeded sample of rows beyond DUMP_BYTES")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
+    if args.full_out is None and args.full:
+        args.full_out = os.path.join(ROOT, "bench_full.json")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -944,7 +983,8 @@ def main():
                     for _ in range(4):
                         step()
                     sync()
-                    probe.setdefault(name, []).append(timed(step, max(10, args.steps), sync) * 1e3)
+                    # (at most PROBE_STEPS per region: the probe's cost must not grow with a long --steps)
+                    probe.setdefault(name, []).append(timed(step, max(10, min(args.steps, PROBE_STEPS)), sync) * 1e3)
             best = min(probe, key=lambda k: min(probe[k]))
             wl.runner.use_graph, wl.pipelined = best == "graph", best == "pipelined"
             picked = {"mode": "auto", "picked": best,
@@ -992,12 +1032,14 @@ def main():
         drift = float((F_last - F_ref).abs().max())
         assert drift < 1e-5, f"descriptors of the last timed step differ from the warm-up step by {drift}"
         bit_reproducible = drift == 0.0
+        if args.dump_outputs and rank == 0:              # (F_last views the bucket's output: before the bucket runs again)
+            dump_outputs(args.dump_outputs, F_last, wl.xyz[(out.first_idx if dyn else wl.last_inds).long()])
 
         # ---- live roofline: --trace-steps further steps, in situ (all three streams), HIP events around every
         # convolution on its launch stream -- AFTER the timed regions
         trace_all = []
         traced_steps = max(1, args.trace_steps)
-        for i in range(traced_steps):
+        for i in range(traced_steps if args.full else 0):
             if dyn:
                 step(trace_all)
             else:
@@ -1009,11 +1051,11 @@ def main():
 
         # ---- SURVEY 8(d)'s span, timed the same way on every rank (host arrays in, descriptors on the host)
         host_span = host_trace = None
-        if not args.no_host_span and dyn:
+        if args.full and not args.no_host_span and dyn:
             pts2, imgs2 = load_pair(args.scale)
             host_span, host_trace = host_span_leg(model, dev, args, barrier, sync, pts2, imgs2, voxel)
         sharded = None
-        if not args.no_sharded and dyn:
+        if args.full and not args.no_sharded and dyn:
             sharded = sharded_pipeline_leg(model, dev, voxel, rank, world, backend, per_rank=args.sharded_per_rank,
                                            min_region_s=args.sharded_region_s, barrier=barrier)
 
@@ -1047,11 +1089,10 @@ def main():
     final = None
     if rank == 0:
         # ---- live roofline of the dominant kernel (HIP events on the launch stream) -------------
-        groups = group_trace(trace, args.arith)
-        extras, arithmetics = {}, None
+        extras, arithmetics, roofline = {}, None, None
         with torch.no_grad():
             iso_groups = None
-            if dyn and world == 1:
+            if args.full and dyn and world == 1:
                 # the same launches with nothing else on the GPU: every stream collapsed onto one (serialised)
                 iso = []
                 for _ in range(3):
@@ -1062,12 +1103,14 @@ def main():
                         wl.bucket.io.serialize = 0
                     sync()
                 iso_groups = group_trace(iso)
-            roofline = build_roofline(groups, args.arith, traced_steps, elapsed / args.steps * 1e3, iso_groups)
-            if world == 1 and not args.no_extras:
+            if args.full:
+                roofline = build_roofline(group_trace(trace, args.arith), args.arith, traced_steps, elapsed / args.steps * 1e3,
+                                          iso_groups)
+            if args.full and world == 1 and not args.no_extras:
                 extras = extra_legs(model, dev, args, sync)
                 arithmetics = other_arithmetics(dev, args, sync, F_ref, pipelined=bool(wl.pipelined))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(xyz1, img1, voxel, sd)
         n_pts = int(wl.xyz.shape[0])
         if host_span:

@@ -5,7 +5,8 @@ container (needs /root/reference); the GPU box and the test-suite use the .npz f
 What it does
   1. copies the reference's *data* fixtures (files/cloud_bin_{0,1}.ply points as float32,
      the two PNGs resized to 120x160, and the xyz rows of files/3D_head_map.ply -- the
-     only result of the path the reference itself pins) into compact .npz files;
+     only result of the path the reference itself pins) into compact .npz files, and
+     files/cloud_bin_0_0.png byte for byte (the native PNG decoder's input);
   2. imports the reference's own model/*.py and util/misc.py VERBATIM over the
      MinkowskiEngine stand-in in oracle/me_shim and a torchvision stub, loads seeded
      weights with strict=True (proves the 361-key state_dict schema), and runs
@@ -15,6 +16,7 @@ What it does
 No reference source text is copied; only inputs and numeric outputs are stored.
 """
 import os
+import shutil
 import sys
 import types
 
@@ -67,6 +69,7 @@ def main():
     np.savez_compressed(f"{HERE}/fixture_images.npz", image_0=images[0], image_1=images[1],
                         png0_rows=mpimg.imread(f"{REF}/files/cloud_bin_0_0.png")[::60, ::80].copy())
     np.savez_compressed(f"{HERE}/head_map_xyz.npz", xyz=head.astype(np.float32))
+    shutil.copyfile(f"{REF}/files/cloud_bin_0_0.png", f"{HERE}/cloud_bin_0_0.png")
 
     # the reference-pinned result: voxelise cloud_bin_0 @2.5cm == 3D_head_map rows
     c25, i25 = O.voxelize(clouds[0].astype(np.float64), 0.025)

@@ -70,3 +70,26 @@ def test_compact_line_without_optional_legs():
     full["rccl"] = {"backend": "nccl", "rccl_ranks": 8, "per_rank_ms_per_step": [1.2] * 8, "gather_crc_ok": None}
     c = bench.compact_line(full)
     assert c["cpu_baseline"] is None and c["rccl"]["rccl_ranks"] == 8 and len(json.dumps(c)) < 3000
+
+
+def test_dump_outputs_writes_the_arrays_or_one_seeded_sample_of_rows(tmp_path, monkeypatch):
+    """--dump-outputs: float32 descriptors and float64 xyz_down as .npy; above DUMP_BYTES the same seeded rows of both."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(1)
+    F, xyz = torch.randn(1000, 32, generator=g), torch.randn(1000, 3, generator=g, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), F, xyz)
+    assert sorted(os.listdir(tmp_path / "all")) == ["descriptors.npy", "xyz_down.npy"]
+    d, x = np.load(tmp_path / "all" / "descriptors.npy"), np.load(tmp_path / "all" / "xyz_down.npy")
+    assert d.dtype == np.float32 and x.dtype == np.float64 and (d == F.numpy()).all() and (x == xyz.numpy()).all()
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * (32 * 4 + 3 * 8 + 8) + 1)
+    for k in (0, 1):
+        bench.dump_outputs(str(tmp_path / str(k)), F, xyz)
+    rows = np.load(tmp_path / "0" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and (np.diff(rows) > 0).all()
+    assert (rows == np.load(tmp_path / "1" / "rows.npy")).all()
+    r = rows.astype(np.int64)
+    assert (np.load(tmp_path / "0" / "descriptors.npy") == F.numpy()[r]).all()
+    assert (np.load(tmp_path / "0" / "xyz_down.npy") == xyz.numpy()[r]).all()
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in os.listdir(tmp_path / "0")) <= bench.DUMP_BYTES + 3 * 128

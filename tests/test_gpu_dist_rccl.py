@@ -60,7 +60,7 @@ def test_gather_of_packed_device_blocks_under_rccl_world_one():
 
 
 def test_bench_multi_rank_path_under_rccl_world_one(tmp_path):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--repeats", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--repeats", "2",
            "--settle-ms", "50", "--mode", "capacity", "--no-cpu-baseline", "--no-extras", "--sharded-per-rank", "12",
            "--sharded-region-s", "0.05", "--full-out", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
