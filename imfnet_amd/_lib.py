@@ -13,6 +13,7 @@ MASK_WORDS = 4
 MAX_KVOL = 125
 MAX_BATCH = 8
 FLAG_RANGE = 32
+XYZ_F32_QUOTIENT = 2      # xyz_is_f64 value: float32 points quantised by the float32 quotient
 
 
 class ImfError(RuntimeError):
@@ -208,6 +209,10 @@ SIGNATURES = {
     "imf_ransac_workspace_bytes": (_Z, [_I]),
     "imf_ransac_registration": (_I, [_P, _L, _P, _L, _P, _I, _D, _D, _I, C.c_uint64, _P, _P, _P, _P, _Z, _P]),
     "imf_gather_points": (_I, [_P, _I, _P, _P, _L, _P, _P]),
+    "imf_icp_workspace_bytes": (_Z, [_L, _L]),
+    "imf_icp_point_to_point": (_I, [_P, _L, _P, _L, _D, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "imf_radius_count_workspace_bytes": (_Z, [_L]),
+    "imf_radius_count": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _P, _P, _Z, _P]),
     "imf_hash_capacity": (_L, [_L]),
     "imf_unique_workspace_bytes": (_Z, [_L]),
     "imf_voxelize": (_I, [_P, _I, _L, _D, _I, _P, _P, _P, _P, _L, _P, _P, _P]),

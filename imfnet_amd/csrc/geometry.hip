@@ -89,7 +89,7 @@ __device__ __forceinline__ void block_bbox_store(int4 lo, int4 hi, int32_t *wg_b
 constexpr int kInsThreads = 256, kInsPerThread = IMF_INS_PPT, kInsPoints = kInsThreads * kInsPerThread, kInsSlots = 2 * kInsPoints;
 static_assert(kInsPerThread % 2 == 0 && kInsSlots <= 65536, "k_insert_points_wg packs two 16-bit LDS slot numbers per word (mine[kInsPerThread / 2])");
 
-template <typename T>
+template <typename T, bool F32Q = false>
 __global__ void __launch_bounds__(kInsThreads)
 k_insert_points_wg(const T *__restrict__ xyz, int64_t n, double voxel, int batch0, const BatchStarts bs,
                    const int32_t *__restrict__ dyn, imf_slot *tab, uint32_t capmask, int32_t *slot_of, int32_t *err,
@@ -123,10 +123,20 @@ k_insert_points_wg(const T *__restrict__ xyz, int64_t n, double voxel, int batch
       } else {
         for (int b = 1; b < nb; ++b) batch += (i >= bs.start[b]) ? 1 : 0;   // items are contiguous point ranges
       }
-      // util/misc.py:82 -- np.floor(xyz / voxel_size) in float64 (IEEE division, exact floor)
-      double fx = floor((double)xyz[3 * i + 0] / voxel);
-      double fy = floor((double)xyz[3 * i + 1] / voxel);
-      double fz = floor((double)xyz[3 * i + 2] / voxel);
+      // util/misc.py:82 -- np.floor(xyz / voxel_size) in float64 (IEEE division, exact floor); F32Q (IMF_XYZ_F32_QUOTIENT,
+      // the KITTI loader's torch.from_numpy(xyz_f32) / voxel_size): the correctly rounded float32 quotient by
+      // (float)voxel, then floor
+      double fx, fy, fz;
+      if (F32Q) {
+        const float vf = (float)voxel;
+        fx = floorf(__fdiv_rn((float)xyz[3 * i + 0], vf));
+        fy = floorf(__fdiv_rn((float)xyz[3 * i + 1], vf));
+        fz = floorf(__fdiv_rn((float)xyz[3 * i + 2], vf));
+      } else {
+        fx = floor((double)xyz[3 * i + 0] / voxel);
+        fy = floor((double)xyz[3 * i + 1] / voxel);
+        fz = floor((double)xyz[3 * i + 2] / voxel);
+      }
       const bool ok = fx >= -kCoordLim && fx < kCoordLim && fy >= -kCoordLim && fy < kCoordLim &&
                       fz >= -kCoordLim && fz < kCoordLim;   // also false for NaN
       if (!ok) {
@@ -507,6 +517,7 @@ int imf_voxelize(const void *xyz, int xyz_is_f64, int64_t n, double voxel_size, 
               "imf_voxelize: null pointer");
   IMF_REQUIRE(n > 0 && n < (1ll << 31) - 2048, "imf_voxelize: n=%lld out of range", (long long)n);
   IMF_REQUIRE(voxel_size > 0.0, "imf_voxelize: voxel_size must be > 0");
+  IMF_REQUIRE(xyz_is_f64 >= 0 && xyz_is_f64 <= IMF_XYZ_F32_QUOTIENT, "imf_voxelize: xyz_is_f64=%d (0, 1 or 2)", xyz_is_f64);
   IMF_REQUIRE(batch_index >= 0 && batch_index < 512, "imf_voxelize: batch_index out of [0,512)");
   IMF_REQUIRE(capacity >= 2 * n && (capacity & (capacity - 1)) == 0 && capacity <= (1ll << 32),
               "imf_voxelize: capacity must be a power of two >= 2n");
@@ -519,7 +530,11 @@ int imf_voxelize(const void *xyz, int xyz_is_f64, int64_t n, double voxel_size, 
   BatchStarts one;
   memset(&one, 0, sizeof(one));
   one.nb = 1;
-  if (xyz_is_f64)
+  if (xyz_is_f64 == IMF_XYZ_F32_QUOTIENT)
+    k_insert_points_wg<float, true><<<nblk, kInsThreads, 0, st>>>((const float *)xyz, n, voxel_size, batch_index, one,
+                                                                  nullptr, table, (uint32_t)(capacity - 1), slot_of, err_out,
+                                                                  nullptr);
+  else if (xyz_is_f64)
     k_insert_points_wg<double><<<nblk, kInsThreads, 0, st>>>((const double *)xyz, n, voxel_size, batch_index, one, nullptr,
                                                              table, (uint32_t)(capacity - 1), slot_of, err_out, nullptr);
   else
@@ -611,6 +626,8 @@ int pyramid_prepare(PyramidBuild &b, const void *xyz, int xyz_is_f64, int64_t n,
   IMF_REQUIRE(n > 0 && n < (1ll << 31) - 2048, "imf_pyramid_build: n=%lld out of range", (long long)n);
   IMF_REQUIRE(n_levels >= 1 && n_levels <= 8, "imf_pyramid_build: n_levels=%d", n_levels);
   IMF_REQUIRE(voxel_size > 0.0, "imf_pyramid_build: voxel_size must be > 0");
+  IMF_REQUIRE(xyz_is_f64 >= 0 && xyz_is_f64 <= IMF_XYZ_F32_QUOTIENT, "imf_pyramid_build: xyz_is_f64=%d (0, 1 or 2)",
+              xyz_is_f64);
   IMF_REQUIRE(batch_index >= 0 && batch_index < 512, "imf_pyramid_build: batch_index out of [0,512)");
   if (row_caps)
     for (int l = 0; l < n_levels; ++l)
@@ -667,7 +684,11 @@ int pyramid_level0(const PyramidBuild &b, hipStream_t st, bool init) {
   const int nblk = (int)div_up(b.n, kInsPoints);
   // [<= div_up(n, 256)][8] inside the unique workspace, 16-byte aligned (slot_of starts 256-byte aligned; k_flag_first reads int4)
   int32_t *const wg_bbox = b.slot_of + (b.n + div_up(b.n, kScanTile) + 16 + 3) / 4 * 4;
-  if (b.xyz_is_f64)
+  if (b.xyz_is_f64 == IMF_XYZ_F32_QUOTIENT)
+    k_insert_points_wg<float, true><<<nblk, kInsThreads, 0, st>>>((const float *)b.xyz, b.n, b.voxel, b.batch_index, bs,
+                                                                  b.dyn, lv[0].table, (uint32_t)(lv[0].capacity - 1),
+                                                                  b.slot_of, b.meta + 1, wg_bbox);
+  else if (b.xyz_is_f64)
     k_insert_points_wg<double><<<nblk, kInsThreads, 0, st>>>((const double *)b.xyz, b.n, b.voxel, b.batch_index, bs, b.dyn,
                                                              lv[0].table, (uint32_t)(lv[0].capacity - 1), b.slot_of,
                                                              b.meta + 1, wg_bbox);
@@ -764,9 +785,10 @@ int imf_pyramid_build_dyn(const void *xyz, int xyz_is_f64, const int32_t *dyn, i
 int imf_gather_points(const void *xyz, int xyz_is_f64, const int32_t *first_idx, const int32_t *m_dev, int64_t m_cap,
                       double *out, void *stream) {
   IMF_REQUIRE(xyz && first_idx && out && m_cap > 0, "imf_gather_points: null pointer");
+  IMF_REQUIRE(xyz_is_f64 >= 0 && xyz_is_f64 <= IMF_XYZ_F32_QUOTIENT, "imf_gather_points: xyz_is_f64=%d", xyz_is_f64);
   hipStream_t st = (hipStream_t)stream;
   const unsigned nb = (unsigned)div_up(3 * m_cap, 256);
-  if (xyz_is_f64) k_gather_points<double><<<nb, 256, 0, st>>>((const double *)xyz, first_idx, m_dev, m_cap, out);
+  if (xyz_is_f64 == 1) k_gather_points<double><<<nb, 256, 0, st>>>((const double *)xyz, first_idx, m_dev, m_cap, out);
   else k_gather_points<float><<<nb, 256, 0, st>>>((const float *)xyz, first_idx, m_dev, m_cap, out);
   IMF_CHECK_LAUNCH("k_gather_points");
   return IMF_OK;

@@ -1,0 +1,448 @@
+// Point-to-point ICP and the radius-count overlap test of the KITTI evaluation (imfnet_amd/evaluate_kitti.py).
+//
+// Reference being replaced (ICP): lib/data_loaders.py:527-556 refines every KITTI ground-truth pose with Open3D 0.12
+// `registration_icp(src, dst, max_corr_dist, init, TransformationEstimationPointToPoint(), ICPConvergenceCriteria(
+// max_iteration))`, relative_fitness = relative_rmse = 1e-6 (the defaults).  Restated here as pinned ([RECALLED] from
+// Open3D's RegistrationICP; no Open3D to check against):
+//   pcd = init . src; corr = correspondences(pcd)
+//   for i < max_iteration:
+//     update = umeyama(corr) (no scaling; identity when corr is empty)
+//     T = update . T
+//     pcd = update . pcd                 (incremental, as pcd.Transform(update): not recomputed from src)
+//     corr = correspondences(pcd)
+//     stop when |d fitness| < 1e-6 and |d rmse| < 1e-6
+// correspondences: every source point gets its nearest target point with d^2 < r^2 (STRICT: FLANN's hybrid
+// search keeps a neighbour whose squared distance is below the squared radius; cKDTree's distance_upper_bound
+// excludes the bound too); equal distances go to the lowest target index.  fitness = n_corr / n_src, rmse =
+// sqrt(sum d^2 / n_corr), both 0 without correspondences.  Reported: T, fitness, rmse of the last correspondence
+// set, the loop iterations run, and n_corr.
+//
+// Reference being replaced (radius count): util/pointcloud.py:56-69 get_matching_indices(pcd0, pcd1, trans,
+// 1.5 voxel), of which the evaluator only uses the length (lib/data_loaders.py:586-588: pairs with fewer than
+// 1000 matches are skipped): the number of pairs (i, j) with |T src_i - dst_j| <= r (the radius search's bound,
+// d^2 <= r^2), and optionally every source point's count.
+//
+// Device design.  The target goes into a uniform grid ONCE per call: cell edge = r, so every point within r of a
+// query lies in the 27 cells around the query's cell (a 125-cell probe at r/2 reads fewer candidates per cell but
+// pays 98 more hash probes per point; on 5 cm KITTI subsets a 0.2 m cell holds a handful of points, the probes
+// dominate).  Cells are keyed through the library's locality-preserving imf_slot hash (common.h): count per cell,
+// one exclusive scan over the table, scatter into a cell-CSR copy of the target (fp64 xyz + original index).  The
+// order of points inside a cell is whatever the scatter's atomics give, which is harmless: the nearest-neighbour
+// choice is (d^2, index)-lexicographic, the count is a count.
+// One ICP iteration is two plain launches: k_icp_corr (one thread per source point: apply the previous update to
+// its current position, search the 27 cells, write the block's fp64 partial sums -- count, sum d^2, sum s, sum d,
+// sum s d^T -- to its own row, no atomics), and k_icp_fit (one workgroup: sums the block rows in a fixed order,
+// fitness / rmse / the convergence test / the Umeyama fit / T = update . T, all fp64).  The host enqueues
+// 2 (max_iteration + 1) launches and never waits inside the loop; once the device's done flag is up, the remaining
+// launches return at once.  No fp64 atomics anywhere: two runs are bit-identical.  No workgroup ever waits for
+// another one.
+#include "common.h"
+#include "registration.h"
+
+namespace imf {
+namespace {
+
+constexpr int kIcpThreads = 256;
+constexpr int kIcpSums = 17;           // count, sum d^2, sum s[3], sum d[3], sum s d^T [9]
+constexpr int kIcpRow = 18;            // doubles per block row (padded)
+constexpr int kFitThreads = 256;
+
+// cell-CSR grid over the target
+struct Grid {
+  imf_slot *tab;                        // key -> (val = first sorted row, pad = count) after the scan
+  uint32_t capmask;
+  int32_t *cnt;                         // [cap] points per slot, then the scatter cursor
+  int32_t *cell_of;                     // [n_dst] slot of every target point
+  double *xyz;                          // [n_dst, 3] target sorted by cell
+  int32_t *idx;                         // [n_dst] original index of every sorted row
+  double inv_cell;
+};
+
+struct IcpInit {
+  double T[16];                         // row-major 4x4, by value (a host matrix)
+};
+
+struct IcpState {
+  double T[16];                         // accumulated transformation, row-major
+  double upd[12];                       // the last update [R | t], applied by the next k_icp_corr
+  double fitness, rmse;
+  int32_t n_corr, iters, done, pad;
+};
+
+__device__ __forceinline__ bool cell_of_point(V3 p, double inv_cell, int lim, int &x, int &y, int &z) {
+  const double fx = floor(p.x * inv_cell), fy = floor(p.y * inv_cell), fz = floor(p.z * inv_cell);
+  if (!(fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim)) return false;   // NaN too
+  x = (int)fx; y = (int)fy; z = (int)fz;
+  return true;
+}
+
+// the slot of a cell key, or -1 (same probe sequence as hash_insert)
+__device__ __forceinline__ int grid_find(const imf_slot *__restrict__ tab, uint32_t capmask, uint64_t key) {
+  uint32_t s = hash_slot(key, 0, capmask);
+  uint32_t step = 0;
+  while (true) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(tab + s);
+    const uint64_t k = ((uint64_t)v.y << 32) | v.x;
+    if (k == key) return (int)s;
+    if (k == kEmptyKey) return -1;
+    if (!step) step = hash_step(key);
+    s = (s + step) & capmask;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_grid_init(imf_slot *tab, int32_t *cnt, int64_t cap, int32_t *err) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) *err = 0;
+  if (i < cap) {
+    reinterpret_cast<uint4 *>(tab)[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+    cnt[i] = 0;
+  }
+}
+
+// target cells are kept one cell inside the key range, so that a query cell's 26 neighbours never wrap
+__global__ __launch_bounds__(256) void k_grid_insert(const double *__restrict__ dst, int64_t n, Grid g, int32_t *err) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int x, y, z;
+  if (!cell_of_point(load3(dst, j), g.inv_cell, kCoordLim - 1, x, y, z)) {
+    atomicOr(err, 1);
+    g.cell_of[j] = -1;
+    return;
+  }
+  const uint32_t s = hash_insert(g.tab, g.capmask, pack_key(0, x, y, z), 0);
+  g.cell_of[j] = (int32_t)s;
+  atomicAdd(&g.cnt[s], 1);
+}
+
+// one workgroup: exclusive scan of the per-slot counts in slot order -> tab[s].val = first row, tab[s].pad = count,
+// cnt[s] = scatter cursor
+__global__ __launch_bounds__(1024) void k_grid_scan(Grid g, int64_t cap) {
+  __shared__ int32_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t per = (cap + 1023) / 1024, b = t * per, e = min(cap, b + per);
+  int32_t sum = 0;
+  for (int64_t s = b; s < e; ++s) sum += g.cnt[s];
+  part[t] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {                 // Hillis-Steele inclusive scan
+    const int32_t v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int32_t run = part[t] - sum;
+  for (int64_t s = b; s < e; ++s) {
+    const int32_t c = g.cnt[s];
+    g.tab[s].val = run;
+    g.tab[s].pad = c;
+    g.cnt[s] = run;
+    run += c;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_grid_scatter(const double *__restrict__ dst, int64_t n, Grid g) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int32_t s = g.cell_of[j];
+  if (s < 0) return;
+  const int32_t r = atomicAdd(&g.cnt[s], 1);
+  g.xyz[3 * (int64_t)r + 0] = dst[3 * j + 0];
+  g.xyz[3 * (int64_t)r + 1] = dst[3 * j + 1];
+  g.xyz[3 * (int64_t)r + 2] = dst[3 * j + 2];
+  g.idx[r] = (int32_t)j;
+}
+
+// nearest target (d^2 < r2, ties -> lowest original index) of p; returns its sorted row or -1
+__device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, double &best_d2) {
+  int x, y, z;
+  best_d2 = 0.0;
+  if (!cell_of_point(p, g.inv_cell, kCoordLim, x, y, z)) return -1;   // beyond every target cell's neighbourhood
+  int best = -1, best_idx = 0x7FFFFFFF;
+  double bd = r2;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+        if (s < 0) continue;
+        const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
+        const int r0 = (int)v.z, r1 = r0 + (int)v.w;
+        for (int r = r0; r < r1; ++r) {
+          const V3 e = sub(load3(g.xyz, r), p);
+          const double d2 = dot(e, e);
+          const int id = g.idx[r];
+          if (d2 < bd || (d2 == bd && best >= 0 && id < best_idx)) {
+            bd = d2; best = r; best_idx = id;
+          }
+        }
+      }
+  best_d2 = bd;
+  return best;
+}
+
+// fixed-order sum of a workgroup's per-thread values (xor butterfly per wavefront, then the 4 wavefronts in order)
+__device__ __forceinline__ double block_sum(double v, double *lds4) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) lds4[w] = v;
+  __syncthreads();
+  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+
+__global__ __launch_bounds__(256) void k_icp_start(const double *__restrict__ src, int64_t n, IcpInit init,
+                                                   double *__restrict__ cur, IcpState *st) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    for (int k = 0; k < 16; ++k) st->T[k] = init.T[k];
+    st->fitness = st->rmse = 0.0;
+    st->n_corr = st->iters = st->done = st->pad = 0;
+  }
+  if (i >= n) return;
+  const V3 p = apply(init.T, load3(src, i));
+  cur[3 * i + 0] = p.x; cur[3 * i + 1] = p.y; cur[3 * i + 2] = p.z;
+}
+
+// stage k: k = 0 on the initial points, k = i + 1 after the update of iteration i
+__global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, double *__restrict__ cur, int64_t n, double r2,
+                                                          int stage, const IcpState *__restrict__ st,
+                                                          double *__restrict__ partial) {
+  if (st->done) return;
+  __shared__ double lds4[4];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double v[kIcpSums];
+#pragma unroll
+  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
+  if (i < n) {
+    V3 p = load3(cur, i);
+    if (stage > 0) {
+      p = apply(st->upd, p);
+      cur[3 * i + 0] = p.x; cur[3 * i + 1] = p.y; cur[3 * i + 2] = p.z;
+    }
+    double d2;
+    const int r = grid_nearest(g, p, r2, d2);
+    if (r >= 0) {
+      const V3 q = load3(g.xyz, r);
+      const double sv[3] = {p.x, p.y, p.z}, dv[3] = {q.x, q.y, q.z};
+      v[0] = 1.0;
+      v[1] = d2;
+      for (int a = 0; a < 3; ++a) {
+        v[2 + a] = sv[a];
+        v[5 + a] = dv[a];
+        for (int b = 0; b < 3; ++b) v[8 + 3 * a + b] = sv[a] * dv[b];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kIcpSums; ++k) {
+    const double s = block_sum(v[k], lds4);
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * kIcpRow + k] = s;
+  }
+}
+
+__global__ __launch_bounds__(kFitThreads) void k_icp_fit(const double *__restrict__ partial, int n_blocks, int64_t n_src,
+                                                         int stage, int max_iteration, IcpState *st, double *out_T,
+                                                         double *out_stats, int32_t *out_meta) {
+  if (st->done) return;
+  __shared__ double lds[kFitThreads];
+  __shared__ double sums[kIcpSums];
+  const int t = threadIdx.x;
+  for (int k = 0; k < kIcpSums; ++k) {
+    double a = 0.0;
+    for (int b = t; b < n_blocks; b += kFitThreads) a += partial[(int64_t)b * kIcpRow + k];   // ascending per thread
+    lds[t] = a;
+    __syncthreads();
+    for (int o = kFitThreads / 2; o > 0; o >>= 1) {     // fixed tree
+      if (t < o) lds[t] += lds[t + o];
+      __syncthreads();
+    }
+    if (t == 0) sums[k] = lds[0];
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double cnt = sums[0];
+  const int n_corr = (int)cnt;
+  const double fitness = n_corr > 0 ? cnt / (double)n_src : 0.0;
+  const double rmse = n_corr > 0 ? sqrt(sums[1] / cnt) : 0.0;
+  int done = 0;
+  if (stage > 0) {
+    st->iters = stage;
+    if (fabs(st->fitness - fitness) < 1e-6 && fabs(st->rmse - rmse) < 1e-6) done = 1;
+  }
+  if (stage >= max_iteration) done = 1;
+  st->fitness = fitness;
+  st->rmse = rmse;
+  st->n_corr = n_corr;
+  if (!done) {
+    double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    if (n_corr > 0) {
+      const double inv = 1.0 / cnt;
+      const V3 ms{sums[2] * inv, sums[3] * inv, sums[4] * inv}, md{sums[5] * inv, sums[6] * inv, sums[7] * inv};
+      const double sv[3] = {sums[2], sums[3], sums[4]}, mdv[3] = {md.x, md.y, md.z};
+      double B[3][3];                                   // sum (s - ms)(d - md)^T = sum s d^T - (sum s) md^T
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) B[a][b] = sums[8 + 3 * a + b] - sv[a] * mdv[b];
+      rigid_from_cov(ms, md, B, U);
+    }
+    double Tn[16];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c)
+        Tn[4 * r + c] = U[4 * r + 0] * st->T[c] + U[4 * r + 1] * st->T[4 + c] + U[4 * r + 2] * st->T[8 + c] +
+                        U[4 * r + 3] * st->T[12 + c];
+    for (int c = 0; c < 4; ++c) Tn[12 + c] = st->T[12 + c];
+    for (int k = 0; k < 16; ++k) st->T[k] = Tn[k];
+    for (int k = 0; k < 12; ++k) st->upd[k] = U[k];
+  }
+  st->done = done;
+  for (int k = 0; k < 16; ++k) out_T[k] = st->T[k];
+  out_stats[0] = fitness;
+  out_stats[1] = rmse;
+  out_meta[0] = st->iters;
+  out_meta[1] = n_corr;
+}
+
+// radius count: one thread per source point, integer totals (order-free)
+__global__ __launch_bounds__(256) void k_radius_count(Grid g, const double *__restrict__ src, int64_t n, IcpInit T, double r2,
+                                                      int32_t *__restrict__ per_point, unsigned long long *total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int c = 0;
+  if (i < n) {
+    const V3 p = apply(T.T, load3(src, i));
+    int x, y, z;
+    if (cell_of_point(p, g.inv_cell, kCoordLim, x, y, z))
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+            if (s < 0) continue;
+            const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
+            for (int r = (int)v.z, r1 = (int)v.z + (int)v.w; r < r1; ++r) {
+              const V3 e = sub(load3(g.xyz, r), p);
+              if (dot(e, e) <= r2) ++c;
+            }
+          }
+    if (per_point) per_point[i] = c;
+  }
+  unsigned long long w = (unsigned long long)c;
+  for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
+  if ((threadIdx.x & 63) == 0 && w) atomicAdd(total, w);
+}
+
+__global__ void k_zero_u64(unsigned long long *p) { *p = 0ull; }
+
+// workspace layout of the grid (all offsets 256-byte aligned)
+struct GridLayout {
+  int64_t cap;
+  size_t tab, cnt, cell_of, xyz, idx, err, total;
+};
+inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
+GridLayout grid_layout(int64_t n_dst) {
+  GridLayout L;
+  L.cap = imf_hash_capacity(n_dst);
+  size_t p = 0;
+  L.tab = p;     p += al256((size_t)L.cap * sizeof(imf_slot));
+  L.cnt = p;     p += al256((size_t)L.cap * 4);
+  L.cell_of = p; p += al256((size_t)n_dst * 4);
+  L.xyz = p;     p += al256((size_t)n_dst * 24);
+  L.idx = p;     p += al256((size_t)n_dst * 4);
+  L.err = p;     p += 256;
+  L.total = p;
+  return L;
+}
+
+int build_grid(const double *dst, int64_t n_dst, double cell, char *ws, Grid &g, int32_t *&err, hipStream_t st) {
+  const GridLayout L = grid_layout(n_dst);
+  g.tab = (imf_slot *)(ws + L.tab);
+  g.capmask = (uint32_t)(L.cap - 1);
+  g.cnt = (int32_t *)(ws + L.cnt);
+  g.cell_of = (int32_t *)(ws + L.cell_of);
+  g.xyz = (double *)(ws + L.xyz);
+  g.idx = (int32_t *)(ws + L.idx);
+  g.inv_cell = (1.0 - 1e-9) / cell;   // a hair over r: rounding in p * inv_cell can never put a point within r two cells away
+  err = (int32_t *)(ws + L.err);
+  k_grid_init<<<(unsigned)div_up(L.cap, 256), 256, 0, st>>>(g.tab, g.cnt, L.cap, err);
+  k_grid_insert<<<(unsigned)div_up(n_dst, 256), 256, 0, st>>>(dst, n_dst, g, err);
+  k_grid_scan<<<1, 1024, 0, st>>>(g, L.cap);
+  k_grid_scatter<<<(unsigned)div_up(n_dst, 256), 256, 0, st>>>(dst, n_dst, g);
+  IMF_CHECK_LAUNCH("imf icp grid build");
+  return IMF_OK;
+}
+
+}  // namespace
+}  // namespace imf
+
+using namespace imf;
+
+extern "C" {
+
+size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst) {
+  if (n_src <= 0 || n_dst <= 0) return 0;
+  const size_t nb = (size_t)div_up(n_src, kIcpThreads);
+  return grid_layout(n_dst).total + al256((size_t)n_src * 24) + al256(nb * kIcpRow * 8) + al256(sizeof(IcpState));
+}
+
+int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
+                           const double *init_host, int max_iteration, double *out_T, double *out_stats,
+                           int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
+  IMF_REQUIRE(src && dst && out_T && out_stats && out_meta && workspace, "imf_icp_point_to_point: null pointer");
+  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst < (1ll << 30),
+              "imf_icp_point_to_point: n_src=%lld n_dst=%lld", (long long)n_src, (long long)n_dst);
+  IMF_REQUIRE(max_corr_dist > 0.0 && max_corr_dist < 1e6, "imf_icp_point_to_point: max_corr_dist=%g", max_corr_dist);
+  IMF_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, "imf_icp_point_to_point: max_iteration=%d", max_iteration);
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_icp_point_to_point: workspace must be 256-byte aligned");
+  IMF_REQUIRE(workspace_bytes >= imf_icp_workspace_bytes(n_src, n_dst), "imf_icp_point_to_point: workspace %zu < %zu",
+              workspace_bytes, imf_icp_workspace_bytes(n_src, n_dst));
+  hipStream_t st = (hipStream_t)stream;
+  char *ws = (char *)workspace;
+  Grid g;
+  int32_t *err;
+  int rc = build_grid(dst, n_dst, max_corr_dist, ws, g, err, st);
+  if (rc) return rc;
+  size_t p = grid_layout(n_dst).total;
+  const int nb = (int)div_up(n_src, kIcpThreads);
+  double *cur = (double *)(ws + p);     p += al256((size_t)n_src * 24);
+  double *partial = (double *)(ws + p); p += al256((size_t)nb * kIcpRow * 8);
+  IcpState *state = (IcpState *)(ws + p);
+  IcpInit init;
+  for (int k = 0; k < 16; ++k) init.T[k] = init_host ? init_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
+  k_icp_start<<<(unsigned)nb, 256, 0, st>>>(src, n_src, init, cur, state);
+  const double r2 = max_corr_dist * max_corr_dist;
+  for (int stage = 0; stage <= max_iteration; ++stage) {
+    k_icp_corr<<<(unsigned)nb, kIcpThreads, 0, st>>>(g, cur, n_src, r2, stage, state, partial);
+    k_icp_fit<<<1, kFitThreads, 0, st>>>(partial, nb, n_src, stage, max_iteration, state, out_T, out_stats, out_meta);
+  }
+  IMF_CHECK_LAUNCH("imf_icp_point_to_point");
+  IMF_CHECK_HIP(hipMemcpyAsync(out_meta + 2, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return IMF_OK;
+}
+
+size_t imf_radius_count_workspace_bytes(int64_t n_dst) {
+  if (n_dst <= 0) return 0;
+  return grid_layout(n_dst).total;
+}
+
+int imf_radius_count(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
+                     int64_t *out_count, int32_t *out_per_point, int32_t *out_err, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+  IMF_REQUIRE(src && dst && out_count && out_err && workspace, "imf_radius_count: null pointer");
+  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst < (1ll << 30),
+              "imf_radius_count: n_src=%lld n_dst=%lld", (long long)n_src, (long long)n_dst);
+  IMF_REQUIRE(r > 0.0 && r < 1e6, "imf_radius_count: r=%g", r);
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_radius_count: workspace must be 256-byte aligned");
+  IMF_REQUIRE(workspace_bytes >= imf_radius_count_workspace_bytes(n_dst), "imf_radius_count: workspace %zu < %zu",
+              workspace_bytes, imf_radius_count_workspace_bytes(n_dst));
+  hipStream_t st = (hipStream_t)stream;
+  Grid g;
+  int32_t *err;
+  int rc = build_grid(dst, n_dst, r, (char *)workspace, g, err, st);
+  if (rc) return rc;
+  IcpInit T;
+  for (int k = 0; k < 16; ++k) T.T[k] = T_host ? T_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
+  unsigned long long *total = reinterpret_cast<unsigned long long *>(out_count);
+  k_zero_u64<<<1, 1, 0, st>>>(total);
+  k_radius_count<<<(unsigned)div_up(n_src, 256), 256, 0, st>>>(g, src, n_src, T, r * r, out_per_point, total);
+  IMF_CHECK_LAUNCH("imf_radius_count");
+  IMF_CHECK_HIP(hipMemcpyAsync(out_err, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return IMF_OK;
+}
+
+}  // extern "C"

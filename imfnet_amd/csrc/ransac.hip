@@ -18,6 +18,7 @@
 // one-sided Jacobi SVD), one wavefront scores each surviving hypothesis over all correspondences, one
 // workgroup picks the winner in a fixed order.
 #include "common.h"
+#include "registration.h"
 
 namespace imf {
 namespace {
@@ -29,96 +30,6 @@ __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
-}
-
-struct V3 {
-  double x, y, z;
-};
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ inline V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline V3 load3(const double *p, long long i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-
-// Rigid fit dst ~ R src + t of n <= 4 pairs (Kabsch / Umeyama without scale): H = sum (s - ms)(d - md)^T
-// = U S V^T, R = V diag(1, 1, det(V U^T)) U^T.  One-sided Jacobi on the columns of H; the column of
-// the smallest singular value is replaced by the cross product of the other two, which is exactly the
-// determinant correction.  T = row-major 3x4 [R | t].
-__device__ void rigid_fit(const V3 *s, const V3 *d, int n, double *T) {
-  V3 ms{0, 0, 0}, md{0, 0, 0};
-  for (int i = 0; i < n; ++i) {
-    ms.x += s[i].x; ms.y += s[i].y; ms.z += s[i].z;
-    md.x += d[i].x; md.y += d[i].y; md.z += d[i].z;
-  }
-  const double inv = 1.0 / n;
-  ms = {ms.x * inv, ms.y * inv, ms.z * inv};
-  md = {md.x * inv, md.y * inv, md.z * inv};
-  double B[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};   // B = H V (starts as H), column k = B[.][k]
-  for (int i = 0; i < n; ++i) {
-    const V3 a = sub(s[i], ms), b = sub(d[i], md);
-    const double av[3] = {a.x, a.y, a.z}, bv[3] = {b.x, b.y, b.z};
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) B[r][c] += av[r] * bv[c];
-  }
-  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0, be = 0, ga = 0;
-        for (int r = 0; r < 3; ++r) {
-          al += B[r][p] * B[r][p];
-          be += B[r][q] * B[r][q];
-          ga += B[r][p] * B[r][q];
-        }
-        off = fmax(off, fabs(ga) / (sqrt(al * be) + 1e-300));
-        if (fabs(ga) <= 1e-300) continue;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-        for (int r = 0; r < 3; ++r) {
-          const double bp = B[r][p], bq = B[r][q];
-          B[r][p] = c * bp - sn * bq;
-          B[r][q] = sn * bp + c * bq;
-          const double vp = V[r][p], vq = V[r][q];
-          V[r][p] = c * vp - sn * vq;
-          V[r][q] = sn * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  double sg[3];
-  for (int k = 0; k < 3; ++k) sg[k] = sqrt(B[0][k] * B[0][k] + B[1][k] * B[1][k] + B[2][k] * B[2][k]);
-  int m = 0;
-  if (sg[1] < sg[m]) m = 1;
-  if (sg[2] < sg[m]) m = 2;
-  const int a = (m + 1) % 3, b = (m + 2) % 3;           // (a, b, m) is a cyclic permutation
-  V3 ua{B[0][a], B[1][a], B[2][a]}, ub{B[0][b], B[1][b], B[2][b]};
-  const double na = sg[a] > 0 ? 1.0 / sg[a] : 0.0, nb = sg[b] > 0 ? 1.0 / sg[b] : 0.0;
-  ua = {ua.x * na, ua.y * na, ua.z * na};
-  ub = {ub.x * nb, ub.y * nb, ub.z * nb};
-  const V3 um = cross(ua, ub);                          // det[ua ub um] = +1
-  const V3 va{V[0][a], V[1][a], V[2][a]}, vb{V[0][b], V[1][b], V[2][b]};
-  const V3 vm = cross(va, vb);                          // V is a rotation: equals its third column
-  const double U3[3][3] = {{ua.x, ub.x, um.x}, {ua.y, ub.y, um.y}, {ua.z, ub.z, um.z}};
-  const double V3m[3][3] = {{va.x, vb.x, vm.x}, {va.y, vb.y, vm.y}, {va.z, vb.z, vm.z}};
-  // H = sum a b^T maps the roles: columns of B live in the "d" space? B = H V with H = A^T-like sum over
-  // a (rows) x b (cols): B columns are combinations of the a-space (rows index a).  R takes s to d:
-  // R = Vd Us^T with Us = left vectors (a-space = source), Vd = right vectors (b-space = destination).
-  double R[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R[r][c] = V3m[r][0] * U3[c][0] + V3m[r][1] * U3[c][1] + V3m[r][2] * U3[c][2];
-  const double msv[3] = {ms.x, ms.y, ms.z}, mdv[3] = {md.x, md.y, md.z};
-  for (int r = 0; r < 3; ++r) {
-    T[4 * r + 0] = R[r][0];
-    T[4 * r + 1] = R[r][1];
-    T[4 * r + 2] = R[r][2];
-    T[4 * r + 3] = mdv[r] - (R[r][0] * msv[0] + R[r][1] * msv[1] + R[r][2] * msv[2]);
-  }
-}
-
-__device__ inline V3 apply(const double *T, V3 p) {
-  return {T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
-          T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]};
 }
 
 // one thread per hypothesis: sample, fit, checkers; valid[it] = 1 and Ts[it] = [R|t] when it survives

@@ -26,7 +26,10 @@ def _cuda_device(device):
     return device
 
 
-def _as_device_points(xyz, device):
+def _as_device_points(xyz, device, quantize="f64"):
+    if quantize == "f32":                             # the float32 quotient needs the float32 values themselves
+        t = xyz if torch.is_tensor(xyz) else torch.from_numpy(np.ascontiguousarray(np.asarray(xyz, dtype=np.float32)))
+        return t.to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
     if torch.is_tensor(xyz):
         t = xyz
     else:
@@ -39,18 +42,21 @@ def _as_device_points(xyz, device):
     return t.to(device, non_blocking=True).contiguous()
 
 
-def start_geometry(xyz, voxel_size, device, inputs_ready=False, item_starts=None):
+def start_geometry(xyz, voxel_size, device, inputs_ready=False, item_starts=None, quantize="f64"):
     """Queue the geometry build of a fragment (upload included when xyz is a host array) and return
     at once.  Handing the result to `sparse_tensor_from_points(geometry=...)` later lets the harness
     build fragment i+1's voxel pyramid while fragment i's decoder is still running.
     A BATCH of fragments (the reference's batched SparseTensor, model/resunet.py:241-250): pass a list of
-    point arrays, or one array holding the items back to back plus `item_starts` (first point of each)."""
+    point arrays, or one array holding the items back to back plus `item_starts` (first point of each).
+    quantize: "f64" (default) -- floor(xyz / voxel) in float64, float32 points widened first (util/misc.py:82, Open3D's
+    float64 points); "f32" -- the points as float32 and the correctly rounded float32 quotient (the KITTI loader's
+    torch.from_numpy(xyz_f32) / voxel_size, lib/data_loaders.py:574-579)."""
     if isinstance(xyz, (list, tuple)):
         dev = torch.device(device)
         on_host = not all(torch.is_tensor(a) and a.is_cuda for a in xyz)
         stream = ops.geometry_stream(dev) if on_host else torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
-            parts = [_as_device_points(a, device) for a in xyz]
+            parts = [_as_device_points(a, device, quantize) for a in xyz]
             if len({t.dtype for t in parts}) > 1:
                 parts = [t.double() for t in parts]
             pts = torch.cat(parts, 0)
@@ -59,19 +65,19 @@ def start_geometry(xyz, voxel_size, device, inputs_ready=False, item_starts=None
             item_starts.append(item_starts[-1] + t.shape[0])
         if not on_host and not inputs_ready:
             pass                                      # the concatenation ran on the current stream: ordered
-        return ops.PyramidFuture(pts, voxel_size, 4, 0, inputs_ready=on_host, item_starts=item_starts)
+        return ops.PyramidFuture(pts, voxel_size, 4, 0, inputs_ready=on_host, item_starts=item_starts, quantize=quantize)
     on_host = not (torch.is_tensor(xyz) and xyz.is_cuda)
     if on_host:                                       # upload on the geometry stream itself: in order
         with torch.cuda.stream(ops.geometry_stream(torch.device(device))):
-            pts = _as_device_points(xyz, device)
+            pts = _as_device_points(xyz, device, quantize)
         inputs_ready = True
     else:
-        pts = _as_device_points(xyz, device)
-    return ops.PyramidFuture(pts, voxel_size, 4, 0, inputs_ready=inputs_ready, item_starts=item_starts)
+        pts = _as_device_points(xyz, device, quantize)
+    return ops.PyramidFuture(pts, voxel_size, 4, 0, inputs_ready=inputs_ready, item_starts=item_starts, quantize=quantize)
 
 
 def sparse_tensor_from_points(xyz, voxel_size, device, feats=None, before_sync=None, inputs_ready=False,
-                              geometry=None):
+                              geometry=None, quantize="f64"):
     """Voxelise raw points on the GPU.  Returns (SparseTensor with all-ones / gathered features,
     inds int32 CUDA tensor of each voxel's first point).
     The whole geometry (voxel hash + 3 coarser levels) is one library call on a dedicated
@@ -79,8 +85,8 @@ def sparse_tensor_from_points(xyz, voxel_size, device, feats=None, before_sync=N
     wait, so independent work (the image branch) is put on the GPU while the host waits for the row
     counts.  `inputs_ready=True` promises that a device-resident `xyz` is already complete (no
     pending producer on the current stream), which lets the geometry of fragment i+1 overlap the
-    convolutions of fragment i."""
-    fut = geometry if geometry is not None else start_geometry(xyz, voxel_size, device, inputs_ready)
+    convolutions of fragment i.  quantize: "f64" (default) or "f32", as in `start_geometry`."""
+    fut = geometry if geometry is not None else start_geometry(xyz, voxel_size, device, inputs_ready, quantize=quantize)
     if before_sync is not None:
         before_sync()
     levels = fut.result()
@@ -183,7 +189,7 @@ FragmentStreamerLanes = 3          # FragmentStreamer's default n_buckets (strea
 
 
 def extract_features_stream(model, fragments, voxel_size, device=None, depth=3, copy=True, batch=2, point_budget=None,
-                            device_sink=None):
+                            device_sink=None, quantize="f64"):
     """`extract_features` over a STREAM of host fragments (SURVEY 8d's span -- host arrays in, descriptors back on the
     host -- pipelined): yields (xyz_down float64 [M,3], F float32 [M,32] numpy) per fragment, in order.  `fragments`:
     iterable of (xyz [N,3] host array, image [1,3,H,W] host array).  Every forward is a job of the library's pipeline
@@ -203,11 +209,16 @@ def extract_features_stream(model, fragments, voxel_size, device=None, depth=3, 
     descriptors as a DEVICE tensor [M, 32] (a view of the capacity bucket's output block, or the exact path's tensor) while
     the runner's main stream is torch's current stream: a copy the sink enqueues there (e.g. into a per-rank send buffer for
     the RCCL gather, dist.gather_fragment_descriptors(packed=...)) is ordered before any later forward that reuses the
-    bucket -- the descriptors go from the bucket to the collective without a host round trip."""
+    bucket -- the descriptors go from the bucket to the collective without a host round trip.
+    quantize="f32" (the KITTI loader's float32 quotient, see `start_geometry`): every fragment takes `extract_features`'
+    exact path, one after the other (the capacity-mode pipeline quantises in float64 only)."""
     from collections import deque
     device = _cuda_device(device or 'cuda:0')
     if model.training:
         model.eval()
+    if quantize != "f64":
+        yield from _stream_exact(model, fragments, voxel_size, device, device_sink, quantize)
+        return
     runner = model.fragment_runner() if hasattr(model, "fragment_runner") else None
     depth = max(1, int(depth))
     if device_sink is not None:
@@ -333,15 +344,27 @@ def extract_features_stream(model, fragments, voxel_size, device=None, depth=3, 
         caller.wait_stream(runner.main_stream(device))
 
 
+def _stream_exact(model, fragments, voxel_size, device, device_sink, quantize):
+    for xyz, image in fragments:
+        with torch.no_grad():
+            xd, F = extract_features(model, xyz, voxel_size=voxel_size, device=device, skip_check=True, image=image,
+                                     quantize=quantize)
+        if device_sink is not None:
+            device_sink(F)
+        yield xd, F.cpu().numpy()
+
+
 def extract_features(model, xyz, rgb=None, normal=None, voxel_size=0.05, device=None,
-                     skip_check=False, is_eval=True, image=None, host_descriptors=True):
+                     skip_check=False, is_eval=True, image=None, host_descriptors=True, quantize="f64"):
     """xyz: [N,3] points (numpy float64/float32, or a tensor already on the device).
     rgb in [0,1] / normal in [-1,1] are optional per-point inputs (concatenated as rgb-0.5, normal/2);
     with neither, the input feature is a column of ones.  image: [1,3,H,W] float32.
     Returns (xyz_down float64 [M,3] on the host, F float32 [M,32] ON THE DEVICE) -- util/misc.py:100-104.  With host arrays
     in, the descriptors are ALSO brought back in the same download as xyz_down (`F.host`, a pinned view valid until the next
     call: it spares the caller's F.cpu(), scripts/generate_desc.py:122); host_descriptors=False leaves them on the device
-    only -- exactly the reference's return, 6.5 MB less over PCIe per S50k fragment."""
+    only -- exactly the reference's return, 6.5 MB less over PCIe per S50k fragment.
+    quantize: "f64" (default, util/misc.py:82) or "f32" (the KITTI loader's float32 quotient of float32 points,
+    lib/data_loaders.py:574-579; see `start_geometry`) -- "f32" runs the exact path, and xyz_down holds the float32 values."""
     if is_eval and model.training:                   # (walking ~190 modules per fragment costs 0.7 ms)
         model.eval()
     if not skip_check:
@@ -368,7 +391,8 @@ def extract_features(model, xyz, rgb=None, normal=None, voxel_size=0.05, device=
 
     # Whole-fragment graph (model/graph.py): no count readback, one launch.  Used once the runner has seen a
     # fragment (it needs voxel-per-point ratios to size its capacity buckets); anything it flags is redone here.
-    runner = model.fragment_runner() if (feats is None and image is not None and hasattr(model, "fragment_runner")) else None
+    runner = model.fragment_runner() if (feats is None and image is not None and quantize == "f64"
+                                         and hasattr(model, "fragment_runner")) else None
     if runner is not None:
         got = _extract_with_runner(runner, xyz, voxel_size, device, image, host_descriptors)
         if got is not None:
@@ -376,17 +400,17 @@ def extract_features(model, xyz, rgb=None, normal=None, voxel_size=0.05, device=
     # descriptor extraction is inference: with is_eval (the reference's callers all sit under torch.no_grad())
     # no autograd graph is recorded, so the packed-plan forward runs instead of the per-layer training path
     with torch.set_grad_enabled(torch.is_grad_enabled() and not is_eval):
-        out = _extract_exact(model, runner, xyz, feats, voxel_size, device, image)
+        out = _extract_exact(model, runner, xyz, feats, voxel_size, device, image, quantize)
         if hasattr(model, "take_flags") and model.take_flags(device) & FLAG_RANGE:
             # an activation left the f16 range of the split-f16 convolutions (it would have become inf): the
             # fragment is redone on the true-fp32 matrix instructions -- slower, never silently wrong
             import warnings
             warnings.warn("imfnet_amd: activation outside the f16 range; fragment recomputed with fp32 MFMA (variant 0)")
-            out = model.forward_fp32(lambda: _extract_exact(model, None, xyz, feats, voxel_size, device, image))
+            out = model.forward_fp32(lambda: _extract_exact(model, None, xyz, feats, voxel_size, device, image, quantize))
     return out
 
 
-def _extract_exact(model, runner, xyz, feats, voxel_size, device, image):
+def _extract_exact(model, runner, xyz, feats, voxel_size, device, image, quantize="f64"):
     """The exact path: geometry with one row-count readback, then the model's forward."""
     start = getattr(model, "start_image_branch", None)
     box = {}
@@ -394,7 +418,7 @@ def _extract_exact(model, runner, xyz, feats, voxel_size, device, image):
         hook = lambda: box.setdefault("image", start(image, device=device))   # noqa: E731
     else:
         hook = None
-    stensor, inds = sparse_tensor_from_points(xyz, voxel_size, device, feats, before_sync=hook)
+    stensor, inds = sparse_tensor_from_points(xyz, voxel_size, device, feats, before_sync=hook, quantize=quantize)
     image_dev = box.get("image")
     if image_dev is None:
         image_dev = torch.as_tensor(image, dtype=torch.float32, device=device)
@@ -405,6 +429,8 @@ def _extract_exact(model, runner, xyz, feats, voxel_size, device, image):
         if getattr(lv[0], "bbox", None) is not None:
             runner.observe(int(xyz.shape[0]), [l.n for l in lv], lv[0].bbox)
 
+    if quantize == "f32":                             # the float32 points the geometry quantised
+        xyz = xyz.float() if torch.is_tensor(xyz) else np.asarray(xyz, dtype=np.float32)
     if torch.is_tensor(xyz) and xyz.is_cuda:          # gather on the device, copy only the M selected rows
         return_coords = xyz.detach()[inds.long()].cpu().numpy().astype(np.float64)
     else:

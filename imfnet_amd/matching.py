@@ -142,3 +142,62 @@ def run_ransac(xyz0, xyz1, feat0, feat1, voxel_size, ransac_n=4, seed=0, device=
     corres = nn_search(f0, f1)
     return ransac_registration(xyz0, xyz1, corres, ransac_n=ransac_n, max_corr_dist=voxel_size * 1.5,
                                edge_similarity=0.9, max_iter=50000, seed=seed, device=device)[0]
+
+
+def _points(x, device, name):
+    t = torch.as_tensor(x).to(device=device, dtype=torch.float64).contiguous()
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] == 0:
+        raise ImfError(f"{name} must be [n>0, 3], got {tuple(t.shape)}")
+    return t
+
+
+def _host_T(T):
+    if T is None:
+        return None
+    return np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4))
+
+
+def icp_point_to_point(src, dst, max_corr_dist, init=None, max_iteration=200, device="cuda"):
+    """Open3D 0.12 registration_icp(src, dst, max_corr_dist, init, TransformationEstimationPointToPoint(),
+    ICPConvergenceCriteria(max_iteration)) on the device (imf_icp_point_to_point; the loop is restated in
+    csrc/icp.hip).  Returns (T 4x4 numpy source->target, fitness, inlier RMSE, iterations run, correspondences)."""
+    s = _points(src, device, "src")
+    d = _points(dst, s.device, "dst")
+    L = _lib.lib()
+    nbytes = L.imf_icp_workspace_bytes(s.shape[0], d.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    T = torch.empty(16, dtype=torch.float64, device=s.device)
+    stats = torch.empty(2, dtype=torch.float64, device=s.device)
+    meta = torch.zeros(3, dtype=torch.int32, device=s.device)
+    init = _host_T(init)
+    check(L.imf_icp_point_to_point(s.data_ptr(), s.shape[0], d.data_ptr(), d.shape[0], float(max_corr_dist),
+                                   init.ctypes.data_as(C.c_void_p) if init is not None else None, int(max_iteration),
+                                   T.data_ptr(), stats.data_ptr(), meta.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "imf_icp_point_to_point")
+    iters, n_corr, err = meta.tolist()
+    if err:
+        raise ImfError("icp_point_to_point: a target point is NaN or beyond the grid's range")
+    fitness, rmse = stats.tolist()
+    return T.cpu().numpy().reshape(4, 4), fitness, rmse, iters, n_corr
+
+
+def radius_count(src, dst, T=None, r=0.45, per_point=False, device="cuda"):
+    """len(get_matching_indices(src, dst, T, r)) of util/pointcloud.py:56-69: the number of pairs (i, j) with
+    |T src_i - dst_j| <= r (imf_radius_count).  Returns the int count, or (count, int32 numpy [n_src] per-point
+    counts) with per_point=True."""
+    s = _points(src, device, "src")
+    d = _points(dst, s.device, "dst")
+    L = _lib.lib()
+    nbytes = L.imf_radius_count_workspace_bytes(d.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    out = torch.zeros(2, dtype=torch.int64, device=s.device)       # [0] count, [1] the error flag (low word)
+    pp = torch.empty(s.shape[0], dtype=torch.int32, device=s.device) if per_point else None
+    Th = _host_T(T)
+    check(L.imf_radius_count(s.data_ptr(), s.shape[0], d.data_ptr(), d.shape[0],
+                             Th.ctypes.data_as(C.c_void_p) if Th is not None else None, float(r), out.data_ptr(),
+                             pp.data_ptr() if per_point else None, out[1:].data_ptr(), ws.data_ptr(), nbytes,
+                             _stream()), "imf_radius_count")
+    count, err = out.tolist()
+    if err & 0xFFFFFFFF:
+        raise ImfError("radius_count: a target point is NaN or beyond the grid's range")
+    return (int(count), pp.cpu().numpy()) if per_point else int(count)

@@ -157,9 +157,15 @@ def geometry_stream(device):
 class PyramidFuture:
     """Geometry of one fragment queued on the geometry stream; `result()` blocks on ITS event only."""
 
-    def __init__(self, xyz, voxel_size, n_levels=4, batch_index=0, inputs_ready=False, item_starts=None):
+    def __init__(self, xyz, voxel_size, n_levels=4, batch_index=0, inputs_ready=False, item_starts=None, quantize="f64"):
         if xyz.dtype not in (torch.float64, torch.float32):
             raise ImfError(f"xyz must be float64/float32, got {xyz.dtype}")
+        if quantize not in ("f64", "f32"):
+            raise ImfError(f"quantize must be 'f64' or 'f32', got {quantize!r}")
+        if quantize == "f32" and xyz.dtype != torch.float32:
+            raise ImfError("quantize='f32' takes float32 points")
+        # xyz_is_f64: 1 float64, 0 float32 widened before the division, 2 float32 quotient (IMF_XYZ_F32_QUOTIENT)
+        mode = _lib.XYZ_F32_QUOTIENT if quantize == "f32" else int(xyz.dtype == torch.float64)
         _req(xyz, xyz.dtype, "xyz", 2)
         n, dev = xyz.shape[0], xyz.device
         if n == 0 or xyz.shape[1] != 3:
@@ -183,12 +189,12 @@ class PyramidFuture:
             self.meta = torch.empty(n_meta, dtype=torch.int32, device=dev)   # counts/flags + bbox (+ item starts)
             if self.n_items > 1:
                 starts = (C.c_int64 * self.n_items)(*[int(v) for v in item_starts])
-                check(L.imf_pyramid_build_batched(xyz.data_ptr(), int(xyz.dtype == torch.float64), n,
+                check(L.imf_pyramid_build_batched(xyz.data_ptr(), mode, n,
                                                   float(voxel_size), starts, self.n_items, n_levels,
                                                   self.arena.data_ptr(), nbytes, self.meta.data_ptr(), self.descs,
                                                   gs.cuda_stream), "imf_pyramid_build_batched")
             else:
-                check(L.imf_pyramid_build(xyz.data_ptr(), int(xyz.dtype == torch.float64), n, float(voxel_size),
+                check(L.imf_pyramid_build(xyz.data_ptr(), mode, n, float(voxel_size),
                                           int(batch_index), n_levels, self.arena.data_ptr(), nbytes,
                                           self.meta.data_ptr(), self.descs, gs.cuda_stream), "imf_pyramid_build")
             self.host.copy_(self.meta, non_blocking=True)

@@ -37,6 +37,7 @@ extern "C" {
 #define IMF_MAX_KVOL     125  /* largest kernel volume (5x5x5, config_3dmatch.py:68) */
 #define IMF_MAX_BATCH    8    /* items of a batched pyramid / forward */
 #define IMF_MASK_WORDS   4    /* 128-bit active-offset mask per tile */
+#define IMF_XYZ_F32_QUOTIENT 2 /* xyz_is_f64 value: float32 points, float32 quotient (imf_voxelize) */
 
 int imf_version(void);
 const char *imf_last_error(void);
@@ -71,8 +72,12 @@ size_t imf_unique_workspace_bytes(int64_t n);
  *           ME.utils.sparse_quantize(coords, return_index=True); ME.utils.batched_coordinates;
  *           and the coordinate-manager insert of ME.SparseTensor(...) at util/misc.py:95.
  * xyz: [n,3] float64 (xyz_is_f64=1) or float32 (=0; widened to double before the division, which is
- *      what Open3D does to the float32 PLY at scripts/generate_desc.py:83,102).
- * Division is IEEE float64, floor() exact => voxel indices are bit-identical to the reference.
+ *      what Open3D does to the float32 PLY at scripts/generate_desc.py:83,102), or float32 with
+ *      xyz_is_f64=IMF_XYZ_F32_QUOTIENT (=2): the quotient is the correctly rounded float32 x / (float)voxel_size,
+ *      then floor -- the KITTI loader's torch.from_numpy(xyz_f32) / voxel_size and numpy's xyz_f32 / 0.05
+ *      (lib/data_loaders.py:532-533, 574-579).  The same three values are accepted wherever a call takes
+ *      xyz_is_f64 (imf_gather_points, the pyramid builds, imf_fragment_io).
+ * Division is IEEE (float64, or float32 in mode 2), floor() exact => voxel indices are bit-identical to the reference.
  * Output rows are in FIRST-OCCURRENCE order (ascending first point index):
  *   coords     int32[n,4]  (only the first *m_out rows are written)
  *   first_idx  int32[n]    index of the first point falling in each voxel (`inds`)
@@ -812,6 +817,31 @@ int imf_ransac_registration(const double *src, int64_t n_src, const double *dst,
                             const int32_t *corres, int ransac_n, double max_corr_dist, double edge_similarity,
                             int max_iter, uint64_t seed, double *out_T, int32_t *out_meta, double *out_stats,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Point-to-point ICP and the radius-count overlap test (the KITTI evaluation, imfnet_amd/evaluate_kitti.py) ----
+ * imf_icp_point_to_point replaces Open3D 0.12 registration_icp(src, dst, max_corr_dist, init,
+ * TransformationEstimationPointToPoint(), ICPConvergenceCriteria(max_iteration)) with the default relative fitness /
+ * RMSE of 1e-6, as lib/data_loaders.py:527-556 refines the KITTI ground truth (the loop restated in csrc/icp.hip):
+ * correspondence = nearest target point with d^2 < max_corr_dist^2 (strict; ties -> lowest target index), Umeyama
+ * update without scaling, incremental transform of the current points, stop when fitness and RMSE both move by
+ * < 1e-6.  src [n_src,3], dst [n_dst,3] device fp64; init_host: HOST pointer, 16 doubles row-major, or NULL =
+ * identity.  Outputs (device): out_T 16 doubles (row-major 4x4 source->target), out_stats double[2] = {fitness,
+ * inlier RMSE}, out_meta int32[3] = {loop iterations run, final correspondences, 1 if a target point was NaN / out of
+ * the grid's range}.  Enqueues 2 (max_iteration + 1) + 5 launches, no host synchronisation; fp64 throughout, no
+ * floating-point atomics: bit-identical from run to run.  workspace: 256-byte aligned. */
+size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst);
+int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
+                           const double *init_host, int max_iteration, double *out_T, double *out_stats,
+                           int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+/* imf_radius_count replaces len(get_matching_indices(pcd0, pcd1, trans, r)) of util/pointcloud.py:56-69 (the
+ * KITTI evaluator's "fewer than 1000 matches" skip, lib/data_loaders.py:586-588): the number of pairs (i, j) with
+ * |T src_i - dst_j| <= r.  T_host: HOST 16 doubles row-major or NULL = identity.  out_count: device int64[1];
+ * out_per_point: optional device int32[n_src], each source point's count; out_err: device int32[1], 1 if a target
+ * point was NaN / out of range.  workspace: imf_radius_count_workspace_bytes(n_dst), 256-byte aligned. */
+size_t imf_radius_count_workspace_bytes(int64_t n_dst);
+int imf_radius_count(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
+                     int64_t *out_count, int32_t *out_per_point, int32_t *out_err, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* ---- Training backward of the sparse convolution (last item) ---------------------------------------
  * Replaces: the backward of ME.MinkowskiConvolution / ConvolutionTranspose under loss.backward(), lib/trainer.py:495-569.
