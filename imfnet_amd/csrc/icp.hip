@@ -22,6 +22,14 @@
 // 1000 matches are skipped): the number of pairs (i, j) with |T src_i - dst_j| <= r (the radius search's bound,
 // d^2 <= r^2), and optionally every source point's count.
 //
+// Reference being replaced (radius pairs): the same get_matching_indices, whose pairs themselves the training data set
+// uses (lib/data_loaders.py:313, positive pairs of the hardest-contrastive loss): every (i, j) with |T src_i - dst_j|
+// <= r, the same bound and transform arithmetic as the count.  FLANN lists a row's hits by distance; here row i's j
+// ascend (the set is identical, the trainer samples from it at random).  Three steps after the grid: the count pass
+// (k_radius_count into a per-point buffer), a one-workgroup int64 scan into CSR offsets, and an emit pass in which
+// every source point fills its own segment and insertion-sorts it by j.  The segment contents do not depend on the
+// scatter's order once sorted: bit-identical from run to run.
+//
 // Device design.  The target goes into a uniform grid ONCE per call: cell edge = r, so every point within r of a
 // query lies in the 27 cells around the query's cell (a 125-cell probe at r/2 reads fewer candidates per cell but
 // pays 98 more hash probes per point; on 5 cm KITTI subsets a 0.2 m cell holds a handful of points, the probes
@@ -329,6 +337,72 @@ __global__ __launch_bounds__(256) void k_radius_count(Grid g, const double *__re
 
 __global__ void k_zero_u64(unsigned long long *p) { *p = 0ull; }
 
+// radius pairs, step 2: one workgroup, exclusive scan of the per-point counts in point order -> offsets[0..n],
+// *out_total = offsets[n].  Each thread owns a contiguous run of points; int64 sums, no atomics.
+__global__ __launch_bounds__(1024) void k_pairs_scan(const int32_t *__restrict__ cnt, int64_t n,
+                                                     int64_t *__restrict__ offsets, int64_t *__restrict__ out_total) {
+  __shared__ int64_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t per = (n + 1023) / 1024, b = t * per, e = min(n, b + per);
+  int64_t sum = 0;
+  for (int64_t i = b; i < e; ++i) sum += cnt[i];
+  part[t] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {                 // Hillis-Steele inclusive scan
+    const int64_t v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int64_t run = part[t] - sum;
+  for (int64_t i = b; i < e; ++i) {
+    offsets[i] = run;
+    run += cnt[i];
+  }
+  if (t == 1023) {
+    offsets[n] = part[1023];
+    *out_total = part[1023];
+  }
+}
+
+// radius pairs, step 3: one thread per source point writes (i, j) for every target within r into its own segment
+// [offsets[i], offsets[i+1]), then insertion-sorts the segment by j.  Nothing is written when the total exceeds the
+// capacity.  The candidate test is k_radius_count's, so the segment fills exactly; the bound check is a guard.
+__global__ __launch_bounds__(256) void k_pairs_emit(Grid g, const double *__restrict__ src, int64_t n, IcpInit T,
+                                                    double r2, const int64_t *__restrict__ offsets, int64_t capacity,
+                                                    int32_t *__restrict__ pairs) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || offsets[n] > capacity) return;
+  const int64_t o0 = offsets[i], o1 = offsets[i + 1];
+  if (o1 == o0) return;
+  int2 *seg = reinterpret_cast<int2 *>(pairs) + o0;
+  const int64_t len = o1 - o0;
+  const V3 p = apply(T.T, load3(src, i));
+  int64_t c = 0;
+  int x, y, z;
+  if (cell_of_point(p, g.inv_cell, kCoordLim, x, y, z))
+    for (int dz = -1; dz <= 1; ++dz)
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+          if (s < 0) continue;
+          const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
+          for (int r = (int)v.z, r1 = (int)v.z + (int)v.w; r < r1; ++r) {
+            const V3 e = sub(load3(g.xyz, r), p);
+            if (dot(e, e) <= r2 && c < len) seg[c++] = make_int2((int32_t)i, g.idx[r]);
+          }
+        }
+  for (int64_t a = 1; a < c; ++a) {                    // a few dozen entries at r = 1.5 voxel
+    const int2 v = seg[a];
+    int64_t b = a - 1;
+    while (b >= 0 && seg[b].y > v.y) {
+      seg[b + 1] = seg[b];
+      --b;
+    }
+    seg[b + 1] = v;
+  }
+}
+
 // workspace layout of the grid (all offsets 256-byte aligned)
 struct GridLayout {
   int64_t cap;
@@ -441,6 +515,53 @@ int imf_radius_count(const double *src, int64_t n_src, const double *dst, int64_
   k_zero_u64<<<1, 1, 0, st>>>(total);
   k_radius_count<<<(unsigned)div_up(n_src, 256), 256, 0, st>>>(g, src, n_src, T, r * r, out_per_point, total);
   IMF_CHECK_LAUNCH("imf_radius_count");
+  IMF_CHECK_HIP(hipMemcpyAsync(out_err, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return IMF_OK;
+}
+
+// radius pairs: workspace = the grid, the per-point counts, the count pass's total
+size_t imf_radius_pairs_workspace_bytes(int64_t n_src, int64_t n_dst) {
+  if (n_src <= 0 || n_dst <= 0) return 0;
+  return grid_layout(n_dst).total + al256((size_t)n_src * 4) + 256;
+}
+
+int imf_radius_pairs(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
+                     int64_t *offsets, int32_t *pairs, int64_t capacity, int64_t *out_total, int32_t *out_err,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+  IMF_REQUIRE(offsets && out_total && out_err, "imf_radius_pairs: null pointer");
+  IMF_REQUIRE(n_src >= 0 && n_dst >= 0 && n_src < (1ll << 30) && n_dst < (1ll << 30),
+              "imf_radius_pairs: n_src=%lld n_dst=%lld", (long long)n_src, (long long)n_dst);
+  IMF_REQUIRE(r > 0.0 && r < 1e6, "imf_radius_pairs: r=%g", r);
+  IMF_REQUIRE(capacity >= 0 && (pairs || capacity == 0), "imf_radius_pairs: capacity=%lld with pairs=%p",
+              (long long)capacity, (const void *)pairs);
+  IMF_REQUIRE(((uintptr_t)pairs & 7) == 0, "imf_radius_pairs: pairs must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_src == 0 || n_dst == 0) {                      // no pairs: zero the outputs, launch nothing
+    IMF_CHECK_HIP(hipMemsetAsync(offsets, 0, (size_t)(n_src + 1) * sizeof(int64_t), st));
+    IMF_CHECK_HIP(hipMemsetAsync(out_total, 0, sizeof(int64_t), st));
+    IMF_CHECK_HIP(hipMemsetAsync(out_err, 0, sizeof(int32_t), st));
+    return IMF_OK;
+  }
+  IMF_REQUIRE(src && dst && workspace, "imf_radius_pairs: null pointer");
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_radius_pairs: workspace must be 256-byte aligned");
+  IMF_REQUIRE(workspace_bytes >= imf_radius_pairs_workspace_bytes(n_src, n_dst),
+              "imf_radius_pairs: workspace %zu < %zu", workspace_bytes, imf_radius_pairs_workspace_bytes(n_src, n_dst));
+  char *ws = (char *)workspace;
+  Grid g;
+  int32_t *err;
+  int rc = build_grid(dst, n_dst, r, ws, g, err, st);
+  if (rc) return rc;
+  size_t p = grid_layout(n_dst).total;
+  int32_t *cnt = (int32_t *)(ws + p);                              p += al256((size_t)n_src * 4);
+  unsigned long long *count_total = (unsigned long long *)(ws + p);
+  IcpInit T;
+  for (int k = 0; k < 16; ++k) T.T[k] = T_host ? T_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
+  const unsigned nb = (unsigned)div_up(n_src, 256);
+  k_zero_u64<<<1, 1, 0, st>>>(count_total);
+  k_radius_count<<<nb, 256, 0, st>>>(g, src, n_src, T, r * r, cnt, count_total);
+  k_pairs_scan<<<1, 1024, 0, st>>>(cnt, n_src, offsets, out_total);
+  k_pairs_emit<<<nb, 256, 0, st>>>(g, src, n_src, T, r * r, offsets, capacity, pairs);
+  IMF_CHECK_LAUNCH("imf_radius_pairs");
   IMF_CHECK_HIP(hipMemcpyAsync(out_err, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   return IMF_OK;
 }

@@ -201,3 +201,49 @@ def radius_count(src, dst, T=None, r=0.45, per_point=False, device="cuda"):
     if err & 0xFFFFFFFF:
         raise ImfError("radius_count: a target point is NaN or beyond the grid's range")
     return (int(count), pp.cpu().numpy()) if per_point else int(count)
+
+
+def _pair_points(x, device, name):
+    t = torch.as_tensor(x).to(device=device, dtype=torch.float64)
+    if t.numel() == 0:
+        t = t.reshape(0, 3)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ImfError(f"{name} must be [n, 3], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def radius_pairs_call(s, d, Th, r, capacity):
+    """One imf_radius_pairs call on device fp64 points.  Returns (pairs int32 [capacity, 2], offsets int64
+    [n_src+1], total, err); the pairs are written only when total <= capacity."""
+    L = _lib.lib()
+    n_src, n_dst = s.shape[0], d.shape[0]
+    nbytes = L.imf_radius_pairs_workspace_bytes(n_src, n_dst)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device) if nbytes else None
+    offsets = torch.empty(n_src + 1, dtype=torch.int64, device=s.device)
+    pairs = torch.empty((capacity, 2), dtype=torch.int32, device=s.device)
+    out = torch.zeros(2, dtype=torch.int64, device=s.device)       # [0] total, [1] the error flag (low word)
+    check(L.imf_radius_pairs(s.data_ptr() if n_src else None, n_src, d.data_ptr() if n_dst else None, n_dst,
+                             Th.ctypes.data_as(C.c_void_p) if Th is not None else None, float(r), offsets.data_ptr(),
+                             pairs.data_ptr() if capacity else None, int(capacity), out.data_ptr(), out[1:].data_ptr(),
+                             ws.data_ptr() if ws is not None else None, nbytes, _stream()), "imf_radius_pairs")
+    total, err = out.tolist()
+    return pairs, offsets, int(total), err & 0xFFFFFFFF
+
+
+def radius_pairs(src, dst, T=None, r=None, device="cuda", capacity=None):
+    """get_matching_indices(src, dst, T, r) of util/pointcloud.py:56-69 on the device (imf_radius_pairs): every (i, j)
+    with |T src_i - dst_j| <= r.  Returns (pairs int32 CUDA [P, 2] = (i, j), offsets int64 CUDA [n_src+1], the CSR row
+    start of every source point).  Within a row j ascends (FLANN orders by distance; the set is the same).  One host
+    read per call; a second call when the first guess of the capacity (32 pairs per source point) was too small."""
+    if r is None:
+        raise ImfError("radius_pairs: r is required")
+    s = _pair_points(src, device, "src")
+    d = _pair_points(dst, s.device, "dst")
+    Th = _host_T(T)
+    cap = int(capacity) if capacity is not None else 32 * s.shape[0]
+    pairs, offsets, total, err = radius_pairs_call(s, d, Th, r, cap)
+    if err:
+        raise ImfError("radius_pairs: a target point is NaN or beyond the grid's range")
+    if total > cap:
+        pairs, offsets, total, err = radius_pairs_call(s, d, Th, r, total)
+    return pairs[:total], offsets

@@ -842,6 +842,19 @@ size_t imf_radius_count_workspace_bytes(int64_t n_dst);
 int imf_radius_count(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
                      int64_t *out_count, int32_t *out_per_point, int32_t *out_err, void *workspace,
                      size_t workspace_bytes, void *stream);
+/* imf_radius_pairs replaces the pairs of get_matching_indices(pcd0, pcd1, trans, r) (util/pointcloud.py:56-69), the
+ * positive pairs of the training data set (lib/data_loaders.py:313): every (i, j) with |T src_i - dst_j| <= r, the bound
+ * and transform arithmetic of imf_radius_count.  offsets: device int64[n_src+1], the CSR row start of every source point
+ * (always written); pairs: device int32[capacity][2] = (i, j), 8-byte aligned, row i's j ascending (FLANN orders a row
+ * by distance; the set is the same).  out_total: device int64[1], always written; when it exceeds capacity no pair is
+ * written (the caller reallocates and calls again).  out_err: device int32[1], 1 if a target point was NaN / out of
+ * range.  n_src == 0 or n_dst == 0: total 0, no kernel launched (workspace may be NULL).  Integer counts, no
+ * floating-point atomics: bit-identical from run to run.  workspace: imf_radius_pairs_workspace_bytes(n_src, n_dst),
+ * 256-byte aligned. */
+size_t imf_radius_pairs_workspace_bytes(int64_t n_src, int64_t n_dst);
+int imf_radius_pairs(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
+                     int64_t *offsets, int32_t *pairs, int64_t capacity, int64_t *out_total, int32_t *out_err,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- Training backward of the sparse convolution (last item) ---------------------------------------
  * Replaces: the backward of ME.MinkowskiConvolution / ConvolutionTranspose under loss.backward(), lib/trainer.py:495-569.
