@@ -14,6 +14,8 @@ MAX_KVOL = 125
 MAX_BATCH = 8
 FLAG_RANGE = 32
 XYZ_F32_QUOTIENT = 2      # xyz_is_f64 value: float32 points quantised by the float32 quotient
+# imf_conv_args.kernel_tag bits: IMF_TAG_* of include/imfnet_hip.h, where each is described (tests check the mirror)
+TAG_LABEL, TAG_REGS, TAG_WAVE8, TAG_WAVE4, TAG_HEAD, TAG_HALF, TAG_U48, TAG_OCC = 1, 2, 4, 8, 16, 64, 128, 256
 
 
 class ImfError(RuntimeError):

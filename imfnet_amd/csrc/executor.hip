@@ -175,78 +175,34 @@ extern "C" {
 static int conv_kernel_tag_rule(int level, int kvol, int cin, int cout, int variant, int n_items);
 
 int imf_resunet_conv_kernel_tag(int level, int kvol, int cin, int cout, int variant, int n_items) {
-  // half tiles (8 | 64): the build for four wavefronts per SIMD (bit 8: 127 VGPRs, 25 KiB of LDS, the partial tiles combined one
-  // row block at a time; the same sums).  Isolated, the shapes of a single fragment 299.8 / 298.2 -> 293.8 / 287.1 us in sum, of a
-  // pair 479 / 488 -> 478 / 464; in the step, A/B three times over on one box: one fragment 0.8367 / 0.8424 / 0.8383 -> 0.8282 /
-  // 0.8296 / 0.8313 ms, a pair (its two up-convolutions) 1.1987 / 1.1955 / 1.1917 -> 1.1930 / 1.1783 / 1.1897.
-  // IMF_HALF_OCC4=0 (diagnostic): the three-wavefront build of round 5.
+  // bf16x3's half tiles run on the build for four wavefronts per SIMD (LAB_NOTES.md 4h-a).  IMF_HALF_OCC4=0 (diagnostic): for three.
   static const bool occ4 = !getenv("IMF_HALF_OCC4") || atoi(getenv("IMF_HALF_OCC4")) != 0;
   const int tag = conv_kernel_tag_rule(level, kvol, cin, cout, variant, n_items);
-  return (occ4 && variant == 3 && (tag & (8 | 64 | 128)) == (8 | 64)) ? (tag | 256) : tag;
+  const int shape = IMF_TAG_WAVE4 | IMF_TAG_HALF | IMF_TAG_U48;
+  return (occ4 && variant == 3 && (tag & shape) == (IMF_TAG_WAVE4 | IMF_TAG_HALF)) ? (tag | IMF_TAG_OCC) : tag;
 }
 
+// The rule as a table, first match wins.  Every line was settled by A/B runs in the step; the figures are in LAB_NOTES.md 4h
+// (the letter at each line: 4h-b ... 4h-g).  IMF_L0_TAG, IMF_L0_UP_TAG, IMF_L1_TAG, IMF_UP_TAG (diagnostic): another tag for that line.
 static int conv_kernel_tag_rule(int level, int kvol, int cin, int cout, int variant, int n_items) {
-  if ((variant != 6 && variant != 0 && variant != 3) || kvol <= 1 || cout % 64 != 0) return 0;   // (variants 0 / 3: the same kernels, other AR)
-  // Stride-1 level: k_spconv_g, except bf16x3's two 64 -> 64 layers (block1_tr): with its weight halves loaded straight
-  // into registers the wave-split kernel takes 126-136 us for such a layer in isolation (half-tile / whole-tile workgroups)
-  // where k_spconv_g takes 136-140 (tools/conv_iso.py, VARIANT=3); in situ the pair step goes 1.259 -> 1.252 ms with whole
-  // tiles and a further -0.7 % with half tiles (A/B/A/B on one box each) -- these two run at the end of the step, when the
-  // side streams are idle.  The 128 -> 64 layer (conv2_tr) loses there (52-56 vs 49 us), and with EVERY stride-1 layer on
-  // the wave-split kernel the step was 1.27 -> 1.33 ms (its workgroups leave no room for the side streams' kernels under
-  // the encoder).
-  // Round 6: 48-ROW UNITS of 4 wavefronts (kernel_tag 8 | 128) instead of half tiles: with the partial tiles combined two row
-  // blocks at a time the workgroup needs 41 KiB of LDS and 145 VGPRs -- three per CU like the half tiles, with 18 KiB of
-  // operands per 72 MFMAs instead of 16 per 48.  In isolation 136-142 -> 124-130 us (whole tiles at two wavefronts per SIMD:
-  // 139-149; at three, kernel_tag 8 | 256: 140-143); pair step, A/B/C/D three times over on one box: half tiles 1.1706 /
-  // 1.1699 / 1.1694, units 1.1640 / 1.1637 / 1.1654, whole tiles x 3: 1.1717 / 1.1609 / 1.1690, x 2: 1.1749 / 1.1779 / 1.1699.
-  // IMF_L0_TAG (diagnostic): another tag for these two layers (72 = half tiles, 264, 8).
-  static const int l0_tag = getenv("IMF_L0_TAG") ? atoi(getenv("IMF_L0_TAG")) : (8 | 128);
-  // ... and (round 6) the stride-1 up-convolution conv2_tr (128 -> 64 over the parity-grouped transposed map) on half tiles of 4
-  // wavefronts built for four per SIMD: round 5's wave-split kernels lost to k_spconv_g there (52-56 vs 49 us), these do not --
-  // headline leg of bench.py, A/B/C/D three times over on one box: k_spconv_g 1.2005 / 1.2076 / 1.2031 ms, half tiles x 4
-  // 1.1693 / 1.1692 / 1.1686 (-2.9 %), 48-row units 1.1680 / 1.1701 / 1.1666, whole tiles 1.1785 / 1.1743 / 1.1762; one fragment
-  // per forward 0.8117 / 0.8177 / 0.8153 -> 0.7689 / 0.7882 / 0.7681.  IMF_L0_UP_TAG (diagnostic): another tag, 0 = k_spconv_g.
-  static const int l0_up_tag = getenv("IMF_L0_UP_TAG") ? atoi(getenv("IMF_L0_UP_TAG")) : (8 | 64);
-  if (level <= 0 && variant == 3 && cin > cout && cout == 64) return l0_up_tag;
-  if (level <= 0) return (variant == 3 && cin == 64 && cout == 64) ? l0_tag : 0;
-  // ONE fragment per forward (the reference's call pattern, resunet.py:163 from generate_desc.py:99): its stride-2/4/8 levels
-  // have 219 / 61 / 17 tiles -- as half-tile workgroups of 4 wavefronts (kernel_tag 8 | 64, spconv_w.hip RB 2) they reach twice
-  // as many CUs: forward 0.93 -> 0.87 ms.  A pair's levels (438 / 120 / 34 tiles) are NOT faster that way (+0.5-1 %: the
-  // wavefronts of a half tile have half the MFMAs per request to hide its latency under) and keep whole tiles.
-  // n_items is static in every mode (the batch of a forward), so exact mode, capacity mode and a replay still agree bit
-  // for bit.
-  {   // (diagnostic, A/B in the step: IMF_L1_TAG replaces the rule for level 1's cin <= cout layers.  Settled the same way and removed
-      // again: overrides for levels 2 / 3 and for the strided convolutions -- LAB_NOTES 4g-10 has the arms.)
-    static const int l1 = getenv("IMF_L1_TAG") ? atoi(getenv("IMF_L1_TAG")) : 0;
-    if (level == 1 && l1 && cin <= cout && variant == 3) return l1;
-  }
-  // Round 6: its stride-4 / 8 levels (61 / 17 tiles) on half tiles of EIGHT wavefronts built for four per SIMD (4 | 64 | 256: two
-  // workgroups per CU, twice the wavefronts on a tile's offset list): 128 -> 128 28.6 -> 23.5 us, 256 -> 256 45.1 -> 36.0,
-  // 128 -> 256 25.2 -> 21.2, 256 -> 128 16.8 -> 14.8; the stride-2 level (219 tiles) stays on 4 wavefronts (23.0 vs 24.5 us).
-  if (variant == 3 && n_items == 1) return level >= 2 ? (4 | 64 | 256) : (8 | 64);
-  // A pair's (or triple's) stride-8 level: 34 tiles x 4 slabs = 136 workgroups for 256 CUs, and every tile-aligned way of
-  // cutting them finer gives 17 x 2^n units.  48-row UNITS that ignore the tile boundaries (kernel_tag 4 | 128, spconv_w.hip
-  // RB 3; a unit walks the union of its two tiles' offset lists) are 46 x 4 = 184 workgroups of 3 / 4 of the work: the
-  // 256 -> 256 layer 67.7 -> 52.2 us, 128 -> 256 38.1 -> 29.5, pair step 1.246 -> 1.215 ms (A/B/A/B on one box).  The stride-4
-  // level (120 tiles x 2 slabs = 240 workgroups already) loses with them (41 -> 58 us).
-  // (the same on fp32 MFMA: 115.7 -> 91.2 us, step 2.00 -> 1.92 ms; split-f16: 38.6 -> 33.7 us, 0.940 -> 0.933 ms)
-  // Larger batches too (units are 3 / 4 of a tile: shorter tails): four fragments per forward 2.197 -> 2.128 ms, eight
-  // 3.978 -> 3.858 ms; and from three fragments on the stride-4 level (>= 180 tiles x 2 slabs: more than one round of
-  // 8-wavefront workgroups) runs on 4-wavefront workgroups, two per CU: 2.128 -> 2.089 ms and 3.858 -> 3.828 ms.
-  if (level == 3 && n_items >= 2) return 4 | 128;
-  if (level == 2 && n_items >= 3) return 8;
-  // the decoder's up-convolutions (cin > cout: conv3_tr 256 -> 64, conv4_tr 256 -> 128): their tiles are grouped by parity
-  // class and walk 1-8 offsets -- short loops, so twice the workgroups help: half tiles 36.1 -> 31.7 us and 24.4 -> 21.8 us
-  // in isolation, pair step -0.8 % (A/B/A/B on one box)
-  static const int up_tag = getenv("IMF_UP_TAG") ? atoi(getenv("IMF_UP_TAG")) : (8 | 64);   // (IMF_UP_TAG: diagnostic)
-  if (variant == 3 && cin > cout) return up_tag;
-  // measured on the S50k pair (profiles/r03_conv_isolated.txt, r05_conv_isolated_*.txt): level 1 (438 tiles) is fastest
-  // with two 4-wavefront workgroups per CU, levels 2 and 3 (<= 128 tiles) with one 8-wavefront workgroup
-  // (round 6, bf16x3: level 1 on the whole-tile build for three wavefronts per SIMD, kernel_tag 8 | 256 -- the same sums; headline
-  // leg of bench.py, A/B four times over on one box: 1.1302 / 1.1331 / 1.1342 / 1.1346 -> 1.1236 / 1.1291 / 1.1316 / 1.1316 ms;
-  // half tiles x 4 there: 1.152, 48-row units 1.157; levels 2 / 3 on half tiles of 8 or 4 wavefronts: +0.3 ... +4 %)
-  if (level == 1) return variant == 3 ? (8 | 256) : 8;
-  return 4;
+  const int W8 = IMF_TAG_WAVE8, W4 = IMF_TAG_WAVE4, HALF = IMF_TAG_HALF, U48 = IMF_TAG_U48, OCC = IMF_TAG_OCC;
+  const bool b3 = variant == 3;
+  if ((variant != 6 && variant != 0 && !b3) || kvol <= 1 || cout % 64 != 0) return 0;   // no wave-split build for the shape
+  static const int l0_tag = getenv("IMF_L0_TAG") ? atoi(getenv("IMF_L0_TAG")) : (W4 | U48);
+  static const int l0_up_tag = getenv("IMF_L0_UP_TAG") ? atoi(getenv("IMF_L0_UP_TAG")) : (W4 | HALF);
+  static const int l1 = getenv("IMF_L1_TAG") ? atoi(getenv("IMF_L1_TAG")) : 0;
+  static const int up_tag = getenv("IMF_UP_TAG") ? atoi(getenv("IMF_UP_TAG")) : (W4 | HALF);
+  // stride 1: k_spconv_g, except on bf16x3 ...
+  if (level <= 0 && b3 && cin > cout && cout == 64) return l0_up_tag;       // ... conv2_tr (128 -> 64, transposed map): half tiles (c)
+  if (level <= 0) return (b3 && cin == 64 && cout == 64) ? l0_tag : 0;      // ... the two 64 -> 64 layers: 48-row units of 4 wavefronts (b)
+  if (level == 1 && l1 && cin <= cout && b3) return l1;                      // (diagnostic only)
+  // one fragment per forward (219 / 61 / 17 tiles): half tiles reach twice the CUs; n_items is static per forward (d)
+  if (b3 && n_items == 1) return level >= 2 ? (W8 | HALF | OCC) : (W4 | HALF);
+  if (level == 3 && n_items >= 2) return W8 | U48;   // stride 8 of a batch (34 tiles x 4 slabs a pair): 48-row units fill more CUs (e)
+  if (level == 2 && n_items >= 3) return W4;         // stride 4 from three fragments on (>= 180 tiles): two workgroups per CU (e)
+  if (b3 && cin > cout) return up_tag;               // up-convolutions: 1-8 offsets per tile, short loops -- twice the workgroups (f)
+  if (level == 1) return b3 ? (W4 | OCC) : W4;       // 438 tiles a pair: two 4-wavefront workgroups per CU; bf16x3 at three per SIMD (g)
+  return W8;                                         // levels 2, 3 (<= 128 tiles): one 8-wavefront workgroup per CU (g)
 }
 
 int imf_resunet_sorted_maps(int variant) {
@@ -749,7 +705,7 @@ int imf_resunet_forward(const imf_resunet_desc *net, const imf_resunet_io *io) {
       a.ev_begin = t.ev_begin; a.ev_end = t.ev_end;
       t.nbr = nullptr; t.kvol = 1; t.cin = h1.cin; t.cout = h1.cout; t.split = 1;
       t.n_slots = rb_id.n_slots; t.n_out = rb_id.n_out; t.launched = 1;
-      t.level = 0; t.slots_extra = 0; t.kernel_tag = 16;
+      t.level = 0; t.slots_extra = 0; t.kernel_tag = IMF_TAG_HEAD;
       io->trace[22].launched = 0;
     }
     if ((rc = imf_pointwise_head(&a, main))) return rc;

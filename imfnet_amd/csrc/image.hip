@@ -315,7 +315,7 @@ int imf_image_branch(const imf_image_desc *net, const float *image, int B, int H
     a.scale = c.scale; a.shift = c.shift; a.residual = residual; a.relu = c.relu; a.out = out;
     a.variant = c.variant; a.split_k = 0;
     a.dyn_err = c.variant == 6 ? flags : nullptr;
-    a.kernel_tag = 1;
+    a.kernel_tag = IMF_TAG_LABEL;
     // 3x3 convolutions of the trunk: the wave-split kernel (one workgroup per tile, the 9 taps x cin/32 sub-stages split
     // over its wavefronts, no split-K partials and no reduce launch).  Measured on the pair's 2 x 120 x 160 images (38 and
     // 10 tiles): branch alone 229 -> 182 us, pair step 1.030 -> 1.018 ms on the same box (14 launches fewer on a chain that
@@ -324,10 +324,10 @@ int imf_image_branch(const imf_image_desc *net, const float *image, int B, int H
     // image size, or an image's features would differ in the last bits between batch sizes.  (This holds for the
     // IMAGE trunk only: the ResUNet's own layers choose their workgroup shape by batch size since round 5,
     // imf_resunet_conv_kernel_tag -- a fragment's descriptors agree between batch sizes to round-off, not bit for bit.)
-    const int waves = c.kvol == 9 && (c.variant == 6 || c.variant == 0 || c.variant == 3) && c.cout % 64 == 0 ? 8 : 0;
-    if (waves == 8) a.kernel_tag = 4 | 1;
-    else if (waves == 4) a.kernel_tag = 8 | 1;
-    if (waves) a.split_k = 1;
+    if (c.kvol == 9 && (c.variant == 6 || c.variant == 0 || c.variant == 3) && c.cout % 64 == 0) {
+      a.kernel_tag |= IMF_TAG_WAVE8;
+      a.split_k = 1;
+    }
     a.workspace = p.splitk; a.workspace_bytes = p.splitk_bytes;
     return imf_spconv_fwd(&a, st);
   };

@@ -281,8 +281,7 @@ k_spconv_mfma(const ConvParams p) {
 // Adds the split-K partial sums in ascending partition order and applies the epilogue.
 // One thread per (slot, 4 output channels).
 __global__ void __launch_bounds__(256)
-k_spconv_reduce(const ConvParams p, int S, long long slot0) {
-  // slots [slot0, n_slots): the whole table for split-K, the balanced tail's tiles otherwise
+k_spconv_reduce(const ConvParams p, int S) {
   if (p.n_out_dev && p.dyn_split_kvol) {   // capacity mode: the main kernel chose the split from the actual rows
     const int cover = S;
     S = auto_split_rule(conv_slots(p, conv_rows(p)), p.cout, p.dyn_split_kvol, p.split_min_blocks, p.split_target);
@@ -291,15 +290,15 @@ k_spconv_reduce(const ConvParams p, int S, long long slot0) {
   }
   const int c4n = p.cout / 4;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long rel = idx / c4n, slot = slot0 + rel, nrel = p.n_slots - slot0;
-  const int c4 = (int)(idx - rel * c4n);
+  const long long slot = idx / c4n;
+  const int c4 = (int)(idx - slot * c4n);
   const bool in_range = slot < p.n_slots;
   const int orow = in_range ? row_of_slot(p, slot) : -1;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (orow >= 0) {
     for (int zz = 0; zz < S; ++zz) {
       const float4 v = *reinterpret_cast<const float4 *>(
-          p.partial + ((long long)zz * nrel + rel) * p.cout + 4 * c4);
+          p.partial + ((long long)zz * p.n_slots + slot) * p.cout + 4 * c4);
       s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     float x[4] = {s.x, s.y, s.z, s.w};
@@ -763,11 +762,7 @@ int imf_spconv_max_split(int cout, int kvol) {
 }
 
 size_t imf_spconv_workspace_bytes(int64_t n_slots, int cout, int split) {
-  if (split > 1) return (size_t)split * (size_t)n_slots * (size_t)cout * sizeof(float);
-  // unsplit launches of >= 512 tiles may balance their last partial round of workgroups (variant 6)
-  const int64_t n_tiles = n_slots / IMF_TILE_ROWS;
-  if (n_tiles < 512 || n_tiles % 256 == 0) return 0;
-  return (size_t)8 * (size_t)(n_tiles % 256) * IMF_TILE_ROWS * (size_t)cout * sizeof(float);
+  return split > 1 ? (size_t)split * (size_t)n_slots * (size_t)cout * sizeof(float) : 0;   // unsplit launches need none
 }
 
 int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
@@ -794,16 +789,15 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   IMF_REQUIRE(!v16 || (a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024),
               "imf_spconv_fwd: variants 6 / 3 need kvol * cin / 32 < %d and <= 1024 channels per source (kvol=%d cin=%d): use variant 0",
               kSubTab, a->kvol, cin);
-  IMF_REQUIRE(a->variant != 3 || (!(a->kernel_tag & 2) && !a->tickets), "imf_spconv_fwd: variant 3 has no register-staged kernel / tickets");
-  // Variant 0 (fp32 MFMA) runs on the LDS-DMA kernels too since round 5 (k_spconv_g / k_spconv_w with AR = kArF32: the
-  // fp32 weight image has the split-f16 image's sub-stage addressing) wherever their tables cover the shape; kernel_tag
-  // bit 1 or `tickets` keep the register-staged round-1 kernel k_spconv_mfma (A/B, the in-launch split-K combine).
-  const bool dma0 = a->variant == 0 && !simple && !(a->kernel_tag & 2) && !a->tickets && a->kvol < kKCache &&
+  IMF_REQUIRE(a->variant != 3 || (!(a->kernel_tag & IMF_TAG_REGS) && !a->tickets), "imf_spconv_fwd: variant 3 has no register-staged kernel / tickets");
+  // Variant 0 (fp32 MFMA) runs on the LDS-DMA kernels too (k_spconv_g / k_spconv_w with AR = kArF32: the fp32 weight image
+  // has the split-f16 image's sub-stage addressing) wherever their tables cover the shape; IMF_TAG_REGS or `tickets` keep
+  // the register-staged kernel k_spconv_mfma (A/B, the in-launch split-K combine).
+  const bool dma0 = a->variant == 0 && !simple && !(a->kernel_tag & IMF_TAG_REGS) && !a->tickets && a->kvol < kKCache &&
                     a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024;
   const bool dma = v16 || dma0;
-  // kernel_tag bits 2 / 3 (variant 6, variant 0 on the DMA kernels): the wave-split kernel (spconv_w.hip) with 8 / 4
-  // wavefronts per workgroup -- the whole tile in one workgroup, no split-K partitions, no reduce launch
-  const int wsplit = dma ? ((a->kernel_tag & 4) ? 8 : ((a->kernel_tag & 8) ? 4 : 0)) : 0;
+  // the wave-split kernel (spconv_w.hip): the whole unit of rows in one workgroup, no split-K partitions, no reduce launch
+  const bool wsplit = dma && (a->kernel_tag & (IMF_TAG_WAVE8 | IMF_TAG_WAVE4));
   if (wsplit) {
     IMF_REQUIRE(a->cout % 64 == 0 && (a->kvol > 1 || cin >= 256),
                 "imf_spconv_fwd: the wave-split kernel needs cout %% 64 == 0 and kvol > 1 or cin >= 256 (kvol=%d cin=%d cout=%d)",
@@ -819,8 +813,7 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   ConvParams p{a->in_a, a->in_b, a->c_a, a->c_b, a->w_packed, a->kvol, a->cout, a->tile_rows,
                a->nbr, a->tile_mask, (long long)a->n_slots, (long long)a->n_out, a->scale, a->shift,
                a->residual, a->relu, a->l2norm, a->out, (float *)a->workspace,
-               ((a->variant == 0 && !simple) || a->variant == 6) ? a->tickets : nullptr, 0};
-  p.tail_begin = p.tail_split = 0;
+               (a->variant == 0 && !simple) ? a->tickets : nullptr};
   p.w_unscale = a->variant == 6 ? a->w_packed + (long long)a->kvol * cin * a->cout + 1 : nullptr;
   p.arith = a->variant == 6 ? kArF16x2 : (a->variant == 3 ? kArBf16x3 : kArF32);
   p.n_out_dev = a->n_out_dev;
@@ -835,71 +828,33 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   p.a_split = (a->operand_format & IMF_FMT_A_SPLIT) ? 1 : 0;
   p.res_split = (a->operand_format & IMF_FMT_RES_SPLIT) ? 1 : 0;
   p.out_split = (a->operand_format & IMF_FMT_OUT_SPLIT) ? 1 : 0;
-  IMF_REQUIRE(!a->operand_format || (a->variant == 6 && split == 1 && !a->tickets && !(a->kernel_tag & 2)),
+  IMF_REQUIRE(!a->operand_format || (a->variant == 6 && split == 1 && !a->tickets && !(a->kernel_tag & IMF_TAG_REGS)),
               "imf_spconv_fwd: operand_format needs variant 6 and an unsplit launch (split_k=%d)", split);
   IMF_REQUIRE(!p.out_split || !a->l2norm, "imf_spconv_fwd: IMF_FMT_OUT_SPLIT not with l2norm");
   IMF_REQUIRE(!p.res_split || a->residual, "imf_spconv_fwd: IMF_FMT_RES_SPLIT without a residual");
   IMF_REQUIRE(!a->geglu || ((v16 || (a->variant == 0 && !simple)) && !wsplit && a->kvol == 1 && a->cout % 64 == 0 &&
-                            split == 1 && !a->scale && !a->residual && !a->relu && !a->l2norm && (dma0 || !(a->kernel_tag & 2))),
+                            split == 1 && !a->scale && !a->residual && !a->relu && !a->l2norm && (dma0 || !(a->kernel_tag & IMF_TAG_REGS))),
               "imf_spconv_fwd: geglu needs variant 6 (k_spconv_g) or 0, kvol 1, cout %% 64 == 0, an unsplit launch and no other epilogue");
-  // XCD-contiguous tile order of k_spconv_g (IMF_G_XCD: bit 0 = the 64-column launches, bit 1 = the 32-column ones; default
-  // both): workgroup b runs on XCD b % 8 and every XCD has its own 4 MiB L2.  In launch order each XCD gathers from ALL input
-  // rows (26 MB for 64 channels at 103 k rows); when XCD x instead walks ONE range of consecutive tiles -- rows are in scan
-  // order, a tile's neighbours sit in nearby tiles -- its L2 serves ~1/8 of the rows.  The ranges are cut from the ACTUAL
-  // tiles on the device (capacity mode; cut from the capacity they left the last XCDs idle: round 2 measured that form
-  // slower), the grid's x extent is padded to a multiple of 8 so that a workgroup's XCD is blockIdx.x & 7.  Same sums.
-  // Measured (round 3, pair step, same box): 0.979 -> 0.955 ms together with the same order in k_spconv_w.
-  const int xcd = 3;
-  // (not for parity-grouped transposed maps: a range of consecutive tiles there is one parity class spread over the whole
-  // level -- no locality to win, measured 43 -> 54 us for conv2_tr)
-  const bool g_xcd = dma && !wsplit && ((CB == 4 && (xcd & 1)) || (CB == 2 && (xcd & 2))) &&
-                     a->n_slots == imf_rulebook_slots(a->n_out);
+  // XCD-contiguous tile order of k_spconv_g: workgroup b runs on XCD b % 8 and every XCD has its own 4 MiB L2, so XCD x
+  // walks ONE range of consecutive tiles (cut from the actual tiles on the device; grid.x padded to a multiple of 8) and its
+  // L2 serves ~1/8 of the input rows.  Same sums.  Not for parity-grouped transposed maps, whose consecutive tiles are one
+  // parity class spread over the whole level.  Measurements: LAB_NOTES.md 4h-h.
+  const bool g_xcd = dma && !wsplit && a->n_slots == imf_rulebook_slots(a->n_out);
   p.no_xcd_swizzle = !g_xcd;
   IMF_REQUIRE(!p.dyn_split_kvol || (!p.tickets && a->split_k >= 1), "imf_spconv_fwd: dyn_split_kvol needs an explicit split_k cover and no tickets");
-#ifndef IMF_WITH_H3
-  if (a->variant == 6 && ((a->kernel_tag & 2) || a->tickets)) {
-    set_error("imf_spconv_fwd: the register-staged variant-6 kernel (kernel_tag bit 1, tickets) is compiled into diagnostic "
-              "builds only (make -C imfnet_amd/csrc h3)");
+  if (a->variant == 6 && ((a->kernel_tag & IMF_TAG_REGS) || a->tickets)) {
+    set_error("imf_spconv_fwd: variant 6 has no register-staged kernel (IMF_TAG_REGS) and no in-launch combine (tickets): "
+              "both belong to variant 0");
     return IMF_EUNSUPPORTED;
   }
-#endif
   dim3 grid((unsigned)(a->n_slots / IMF_TILE_ROWS), (unsigned)(a->cout / (16 * CB)), (unsigned)split);
   if (g_xcd) grid.x = (grid.x + 7u) / 8u * 8u;
   hipStream_t st = (hipStream_t)stream;
   if (a->ev_begin) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)a->ev_begin, st));
   if (wsplit) {
-    launch_spconv_w(p, grid.x, wsplit, st, (a->kernel_tag & 1) | ((a->kernel_tag & 64) ? 2 : 0) | ((a->kernel_tag & 128) ? 4 : 0) |
-                                             ((a->kernel_tag & 256) ? 8 : 0));
-  } else if (dma0 || a->variant == 3) {
-    launch_spconv_g(p, grid, CB, st, a->kernel_tag & 1);
-  } else if (a->variant == 6) {
-    // Balanced tail: with >= 2 full rounds of workgroups per CU and a partial last round (801 tiles on
-    // 256 CUs: 33 CUs get a 4th tile and set the kernel time), the tail tiles are split over their
-    // offsets so every CU receives the same work.  Needs a little workspace; skipped without it.
-    // Measured (S50k): the two 64->64 layers drop 61 -> 56 us, but the extra reduce launch takes the
-    // step-level gain back (0.886 vs 0.884 ms), so it is opt-in: IMF_CONV_TAIL=1.
-#ifdef IMF_WITH_H3
-    static const int tail_env = getenv("IMF_CONV_TAIL") ? atoi(getenv("IMF_CONV_TAIL")) : 0;
-#else
-    const int tail_env = 0;                                    // the balanced tail lives in k_spconv_h3 (diagnostic builds)
-#endif
-    const long long n_tiles = grid.x;
-    const int tail_tiles = (int)(n_tiles % 256);
-    const int ts = a->kvol >= 16 ? 8 : 4;
-    // (not for parity-grouped transposed rulebooks: their slot order comes from atomics, and splitting
-    // only SOME tiles would make a row's rounding depend on where it landed -- bit-reproducibility)
-    const bool fixed_order = a->n_slots == imf_rulebook_slots(a->n_out);
-    if (tail_env && fixed_order && split == 1 && grid.y == 1 && a->kvol >= 8 && n_tiles >= 512 && tail_tiles > 0 &&
-        a->workspace && a->workspace_bytes >= (size_t)ts * tail_tiles * IMF_TILE_ROWS * a->cout * sizeof(float)) {
-      p.tail_begin = (int)(n_tiles - tail_tiles);
-      p.tail_split = ts;
-      grid.x = (unsigned)(p.tail_begin + tail_tiles * ts);
-    }
-#ifdef IMF_WITH_H3
-    launch_spconv_h3(p, grid, CB, st, a->kernel_tag);          // diagnostic build: register-staged twin / stamps / tickets
-#else
-    launch_spconv_g(p, grid, CB, st, a->kernel_tag & 1);
-#endif
+    launch_spconv_w(p, grid.x, a->kernel_tag, st);
+  } else if (dma) {
+    launch_spconv_g(p, grid, CB, st, a->kernel_tag & IMF_TAG_LABEL);
   } else if (simple) {
     if (CB == 4 && J == 4)      k_spconv_mfma_simple<4, 4><<<grid, 256, 0, st>>>(p);
     else if (CB == 4 && J == 2) k_spconv_mfma_simple<4, 2><<<grid, 256, 0, st>>>(p);
@@ -913,15 +868,9 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   }
   IMF_CHECK_LAUNCH("k_spconv_mfma");
   if (a->ev_end) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)a->ev_end, st));
-  if (p.tail_split > 1) {
-    const long long slot0 = (long long)p.tail_begin * IMF_TILE_ROWS;
-    const long long total = (a->n_slots - slot0) * (a->cout / 4);
-    k_spconv_reduce<<<(unsigned)div_up(total, 256), 256, 0, st>>>(p, p.tail_split, slot0);
-    IMF_CHECK_LAUNCH("k_spconv_reduce");
-  }
   if (split > 1 && !p.tickets) {
     const long long total = (long long)a->n_slots * (a->cout / 4);
-    k_spconv_reduce<<<(unsigned)div_up(total, 256), 256, 0, st>>>(p, split, 0);
+    k_spconv_reduce<<<(unsigned)div_up(total, 256), 256, 0, st>>>(p, split);
     IMF_CHECK_LAUNCH("k_spconv_reduce");
   }
   return IMF_OK;

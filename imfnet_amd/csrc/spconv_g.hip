@@ -1,9 +1,10 @@
 // Sparse convolution, variant 6, second implementation: both operands go global -> LDS directly
-// (`buffer_load_dwordx4 ... lds`, no VGPR destination); same arithmetic as k_spconv_h3, bit for bit.
+// (`buffer_load_dwordx4 ... lds`, no VGPR destination); same arithmetic, bit for bit, as the register-staged kernel it
+// replaced (retired; its measurements: LAB_NOTES.md 4, its source: git history).
 //
-// Why (round 2; tools/ubench/gather_shape.hip, profiles/r02_gather_shape.txt): k_spconv_h3 is bound by the
+// Why (round 2; tools/ubench/gather_shape.hip, profiles/r02_gather_shape.txt): the register-staged kernel was bound by the
 // vector-memory RETURN path of the CU, not by L2 / HBM, the matrix pipe or instruction issue.  Per wavefront and
-// 16 KiB stage it issues four row gathers in MFMA-fragment shape (lane l: row l & 15, 16-byte piece l >> 4) and four
+// 16 KiB stage it issued four row gathers in MFMA-fragment shape (lane l: row l & 15, 16-byte piece l >> 4) and four
 // contiguous 1 KiB weight loads, all into VGPRs.  Measured per wave-level load and CU on L2-resident data:
 //   fragment-shaped gather -> VGPRs      31 cycles (52 % of the rows present)
 //   contiguous 1 KiB block -> VGPRs      28 cycles
@@ -24,8 +25,7 @@
 // (checked on the hardware by the micro-benchmark).  Everything lives in ONE __shared__ array: with a second
 // object hipcc 7.2 drains the DMA queue before every ds_read.
 //
-// Not covered here (launch_spconv_h3 keeps them on k_spconv_h3): the in-launch split-K combine (tickets), the
-// balanced tail, the s_memtime stamps.
+// Not covered here: the in-launch split-K combine (tickets) -- variant 0's register-staged k_spconv_mfma (spconv.hip) has it.
 #include "spconv_shared.h"
 
 #ifndef IMF_G_ABL
@@ -53,7 +53,7 @@ typedef __attribute__((address_space(3))) void lds_void;
 namespace {
 
 constexpr int kDummyJk = kKCache - 1;        // neighbour-table row that is always "no input"
-constexpr unsigned kNoRow = 0x00FFFFFFu;     // see spconv_h3.hip
+constexpr unsigned kNoRow = 0x00FFFFFFu;     // 24-bit row index whose byte offset falls outside the buffer window
 
 __device__ __forceinline__ void split8(const float4 &x0, const float4 &x1, f16x8 &hi, f16x8 &lo) {
   const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
@@ -87,13 +87,13 @@ __device__ __forceinline__ f16x8 lds_read_f16x8(const float4 *__restrict__ src) 
 // wavefront two row blocks against one read of the B fragments (12 instead of 20 KiB of LDS reads per 32 rows and
 // sub-stage, one weight copy per 128 rows).  Sums stay bit-identical: each tile keeps its OWN partition of its own
 // active offsets (an offset outside it reads as "no input" for that tile's rows), and every accumulator sees the same
-// MFMA sequence as in k_spconv_h3.
+// MFMA sequence as with RB 1.
 //
-// Two further schedules were built on this kernel, measured bit-identical and SLOWER, and live in
-// tools/experiments/spconv_g_rb2_pipe.hip: RB 2 as a launch option (64 -> 64 at 103 k rows 93 -> 97 us; the transposed
+// Two further schedules were built on this kernel and measured bit-identical and SLOWER (LAB_NOTES.md 4c; sources in git
+// history): RB 2 as a launch option (64 -> 64 at 103 k rows 93 -> 97 us; the transposed
 // maps up to 1.6x slower: only two workgroups fit a CU) and register double-buffering of the LDS -> VGPR fragment reads
 // (93 -> 98 us at 121 VGPRs).  A third one, eight-wavefront workgroups sharing one weight block between two tiles (DMA
-// instructions per row -25 % at the same 16 wavefronts per CU; tools/experiments/spconv_g_tw2.hip), was bit-identical
+// instructions per row -25 % at the same 16 wavefronts per CU), was bit-identical
 // and slower too (91 -> 99 us).  RB 2 was tried once more on operand images (PRE, no conversions left in the loop; round 3):
 // bit-identical, pair step 0.989 -> 1.001 ms.  Only RB 1 with four wavefronts is instantiated here.
 //
@@ -207,7 +207,7 @@ k_spconv_g(const ConvParams p) {
   if (tid < 32 && ((uni >> tid) & 1u)) klist[__builtin_popcount(uni & ((1u << tid) - 1u))] = tid;
   __syncthreads();
   const int n_sub = (IMF_G_ABL & 16) ? 0 : nk * ncc;
-  {   // the tiles' slice of the neighbour table as 24-bit row indices, and the sub-stage table (spconv_h3.hip).
+  {   // the tiles' slice of the neighbour table as 24-bit row indices, and the sub-stage table.
       // The loads are unconditional (clamped offset index, clamped tile) and sit outside any per-element branch: a
       // "load or constant" select per element makes hipcc 7.2 branch around every load and wait for each one --
       // seven dependent memory round trips per workgroup instead of one.
@@ -455,7 +455,7 @@ k_spconv_g(const ConvParams p) {
           acc[b][cb][0] += (float)bh[cb][0] + (float)bl[cb][1] + (float)ah[b][0] + (float)al[b][1];
       continue;
     }
-    // per accumulator the order of k_spconv_h3: lo*hi, hi*lo, hi*hi; consecutive MFMAs on different accumulators
+    // per accumulator, smallest terms first: lo*hi, hi*lo, hi*hi; consecutive MFMAs on different accumulators
 #pragma unroll
     for (int b = 0; b < RB; ++b)
 #pragma unroll

@@ -9,8 +9,7 @@
 // accuracy (the dropped lo*lo term is 2^-22 relative; measured end to end: max |dF| 3e-7 against an
 // fp64-accumulated network, plain fp32 is 2e-7).  Inputs must stay below the f16 range (65 504) --
 // guarded by IMF_FLAG_RANGE; the weights are split once, here, at pack time.  The kernels that consume the image:
-// spconv_g.hip (LDS-DMA staging, level 0 and the image branch), spconv_w.hip (wave-split, coarse levels), head.hip,
-// and -- diagnostic builds only -- the register-staged spconv_h3.hip.
+// spconv_g.hip (LDS-DMA staging, level 0 and the image branch), spconv_w.hip (wave-split, coarse levels), head.hip.
 #include "spconv_shared.h"
 
 namespace imf {

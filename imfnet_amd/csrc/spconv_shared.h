@@ -1,4 +1,4 @@
-// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_h3.hip).
+// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_g.hip, spconv_w.hip).
 #pragma once
 #include "common.h"
 
@@ -49,11 +49,6 @@ struct ConvParams {
   float *partial;   // split-K partial sums [S][n_slots][cout] (S = gridDim.z > 1)
   int *tickets;     // optional arrival counters [n_tiles][n_slabs] (zero on entry, left zero): the last
                     // partition to arrive reduces the tile in-kernel instead of a second launch
-  int ablate;       // debugging only (env IMF_ABLATE): bit0 no MFMA, bit1 no LDS add, bit2 no A gather, bit3 no B load
-  // Tail balancing (variant 6, gridDim.z == 1): tiles >= tail_begin are split tail_split ways over their
-  // active offsets so that the last, partial round of workgroups per CU is made of small pieces; their
-  // partial sums live in `partial` as [tail_split][n_slots - 64 tail_begin][cout].  0 = off.
-  int tail_begin, tail_split;
   // variant 6: the split-f16 weight image is stored scaled by a power of two (so that the lo halves stay
   // normal f16 numbers); *w_unscale = 2^-s is multiplied back into the fp32 accumulators (exact).  NULL = 1.
   const float *w_unscale;
@@ -65,8 +60,10 @@ struct ConvParams {
   int dyn_split_kvol;       // third argument of the split rule (active offsets per tile); 0 = gridDim.z is the split
   int slots_extra;          // slots the rulebook lays out beyond roundup64(rows): 0, or 512 for transposed maps
   int split_min_blocks, split_target;
-  int no_xcd_swizzle;       // A/B switch (env IMF_H3_NO_XCD): plain blockIdx.x -> tile order
-  int w_xcd;                // k_spconv_w: slab = f(XCD) workgroup order (env IMF_W_XCD)
+  int no_xcd_swizzle;       // k_spconv_g: plain blockIdx.x -> tile order instead of one range of consecutive tiles per XCD
+                            // (imf_spconv_fwd: wave-split launches, transposed maps)
+  int w_xcd;                // k_spconv_w's workgroup order: 2 = slab by XCD and one range of consecutive tiles per XCD,
+                            // 1 = slab by XCD, tiles interleaved (transposed maps); set by launch_spconv_w
   int geglu;                // epilogue of the fusion block's first feed-forward GEMM (variant 6, 64-column slabs, unsplit): the
                             // packed columns of slab y are [32 values | 32 gates] of hidden units 32 y .. 32 y + 31; the output
                             // is [n_out, cout / 2]: out = (v + shift_v) * gelu(g + shift_g), exact-erf GELU
@@ -374,14 +371,13 @@ __device__ __forceinline__ void fused_reduce_tile(const ConvParams &p, int S, lo
 constexpr int kKCache = 28;   // active offsets cached per workgroup (kvol <= 27 uses the pipelined kernels)
 constexpr int kSubTab = 27 * 8 + 8;   // variant 6: sub-stage table entries per workgroup; kvol * cin / 32 must stay below it
 
-// spconv_h3.hip: variant 6 (split-f16 MFMA); grid = (tiles, cout / (16 CB), split)
-void launch_spconv_h3(const ConvParams &p, dim3 grid, int co_blk, hipStream_t st, int use = 0);
-// spconv_g.hip: the same arithmetic with both operands staged by LDS-DMA (default; launch_spconv_h3 dispatches)
+// spconv_g.hip: variants 6 / 3 / 0 with both operands staged by LDS-DMA; grid = (tiles, cout / (16 CB), split)
 void launch_spconv_g(const ConvParams &p, dim3 grid, int co_blk, hipStream_t st, int use = 0);
 
-// spconv_w.hip: variant 6 for the coarse levels -- one workgroup per (tile, 64-column slab), the tile's sub-stages split
-// over its `waves` (8 or 4) wavefronts, partial tiles combined through LDS, epilogue in the same launch
-void launch_spconv_w(const ConvParams &p, unsigned tiles, int waves, hipStream_t st, int use = 0);
+// spconv_w.hip: the same arithmetic for the coarse levels -- one workgroup per (unit of rows, 64-column slab), the unit's
+// sub-stages split over its wavefronts, partial tiles combined through LDS, epilogue in the same launch.  `tag` is
+// imf_conv_args.kernel_tag as the caller gave it (IMF_TAG_WAVE8 or IMF_TAG_WAVE4 set); `tiles` = 64-row tiles of the map
+void launch_spconv_w(const ConvParams &p, unsigned tiles, int tag, hipStream_t st);
 
 // spconv.hip: imf_conv_first_bitgrid_dyn on a grid the caller already zeroed and filled (geometry.hip: k_emit_unique)
 // the fusion block with its output optionally written as a split-f16 operand image (fusion.hip; for imf_resunet_forward)

@@ -329,8 +329,7 @@ k_spconv_w(const ConvParams p) {
     // (Round 6, measured and dropped again, this time WITHOUT register copies: the whole weight block of t + 1 requested at the
     // head of t into a second register pair, loop unrolled by two, pairs alternating by code -- 226 VGPRs, bit-identical; whole
     // tiles 64 -> 64 at 103 k rows 147 -> 151 us, 8 wavefronts 151 -> 172, 48-row units 147 -> 178, pair step 1.204 -> 1.257 ms:
-    // more requests in flight delay the row pieces more than the earlier weights help.  tools/experiments/
-    // spconv_w_full_stage_prefetch.hip)
+    // more requests in flight delay the row pieces more than the earlier weights help.  LAB_NOTES.md 4g-7)
     bf16x8 bA[2][3], bB[2][3];
     if (t0 < t1) IMF_W_LD_WHALF(bA, e_cur, 0)
 #pragma unroll 1
@@ -545,79 +544,60 @@ k_spconv_w(const ConvParams p) {
   }
 }
 
-// grid = (tiles, cout / 64); `waves` = 8 (512 threads, one workgroup per CU) or 4 (256 threads, two per CU)
-void launch_spconv_w(const ConvParams &p_in, unsigned tiles, int waves, hipStream_t st, int use) {
-  // use bit 1: half-tile workgroups (RB 2; bf16x3: 4 wavefronts, with bit 3 also 8); bit 2: 48-row units (RB 3; 8 wavefronts, bf16x3
-  // also 4); bit 3 (bf16x3): the build for one more wavefront per SIMD -- whole tiles of 4 wavefronts for three, half tiles for four
-  const bool half8 = (use & 2) != 0 && (use & 8) != 0 && waves == 8 && p_in.arith == kArBf16x3;   // half tiles of 8 wavefronts, two workgroups per CU
-  const bool half = ((use & 2) != 0 && waves == 4 && p_in.arith == kArBf16x3) || half8;
-  const bool u48 = (use & 4) != 0 && (waves == 8 || (waves == 4 && p_in.arith == kArBf16x3)) && !half;
-  const bool occ_bit = (use & 8) != 0;
-  const bool occ3 = occ_bit && waves == 4 && p_in.arith == kArBf16x3 && !half && !u48;   // whole tiles, three wavefronts per SIMD
-  use &= 1;
-  if (half) tiles *= 2;
-  if (u48) tiles = (tiles * 4u + 2u) / 3u;
-  // w_xcd 1 = slab by XCD, tiles interleaved (pair step 1.092 -> 1.074 ms, round 3); 2 = slab by XCD AND one range of
-  // consecutive tiles per XCD (0.953 -> 0.940 ms on top: the XCD's L2 serves a fraction of the input rows)
-  const int xcd_env = 2;
+// Which build of k_spconv_w a launch takes: the template arguments W / USE / RB / OCC, and the number of workgroups along x.
+struct WBuild {
+  int waves, label, rb, occ;
+  unsigned units;
+};
+
+// The one place that reads the workgroup-shape bits of imf_conv_args.kernel_tag (include/imfnet_hip.h, IMF_TAG_*).  A bit
+// without a build for the launch's arithmetic is ignored: half tiles and the builds for one more wavefront per SIMD exist
+// for bf16x3 only; 48-row units of 4 wavefronts too; the profiling label only for whole tiles of 8 wavefronts at two per
+// SIMD, without a concatenated input.  Half tiles win over 48-row units, either over IMF_TAG_OCC's whole-tile build.
+static WBuild w_build_of(int tag, int arith, bool cat, unsigned tiles) {
+  const int waves = (tag & IMF_TAG_WAVE8) ? 8 : 4;
+  const bool b3 = arith == kArBf16x3, occ = (tag & IMF_TAG_OCC) != 0;
+  if (b3 && (tag & IMF_TAG_HALF) && (waves == 4 || occ))        // 8 wavefronts: the four-per-SIMD build only
+    return {waves, 0, 2, occ ? 4 : 3, tiles * 2u};
+  if ((tag & IMF_TAG_U48) && (waves == 8 || b3))                 // 4 wavefronts (bf16x3): three per SIMD as built
+    return {waves, 0, 3, waves == 4 ? 3 : 2, (tiles * 4u + 2u) / 3u};
+  if (b3 && occ && waves == 4) return {4, 0, 4, 3, tiles};
+  return {waves, (tag & IMF_TAG_LABEL) && waves == 8 && !cat ? 1 : 0, 4, 2, tiles};
+}
+
+template <int AR>
+static void launch_w_build(const WBuild &b, bool cat, dim3 grid, hipStream_t st, const ConvParams &p) {
+#define IMF_W_BUILD(W, RB, OCC)                                                               \
+  if (b.waves == W && b.rb == RB && b.occ == OCC && !b.label) {                               \
+    if (cat) k_spconv_w<true, W, AR, 0, RB, OCC><<<grid, 64 * W, 0, st>>>(p);                 \
+    else     k_spconv_w<false, W, AR, 0, RB, OCC><<<grid, 64 * W, 0, st>>>(p);                \
+    return;                                                                                   \
+  }
+  if (b.label) { k_spconv_w<false, 8, AR, 1, 4, 2><<<grid, 512, 0, st>>>(p); return; }
+  IMF_W_BUILD(8, 4, 2) IMF_W_BUILD(4, 4, 2) IMF_W_BUILD(8, 3, 2)
+  if constexpr (AR == kArBf16x3) {
+    IMF_W_BUILD(8, 2, 4) IMF_W_BUILD(4, 2, 4) IMF_W_BUILD(4, 2, 3) IMF_W_BUILD(4, 3, 3) IMF_W_BUILD(4, 4, 3)
+  }
+#undef IMF_W_BUILD
+}
+
+// grid = (units, cout / 64); 8 wavefronts = 512 threads, 4 = 256
+void launch_spconv_w(const ConvParams &p_in, unsigned tiles, int tag, hipStream_t st) {
   ConvParams p = p_in;
-  // (a transposed map's tiles are grouped by parity class: consecutive tiles there are not neighbours in space -- mode 1)
-  const bool transposed = p.n_slots != (p.n_out + IMF_TILE_ROWS - 1) / IMF_TILE_ROWS * IMF_TILE_ROWS;
-  // (round 6, in the step with conv2_tr on this kernel: mode 1 for transposed maps 1.1277 / 1.1254 ms, mode 2: 1.1706 / 1.1712, plain order 1.1339 / 1.1331)
-  p.w_xcd = xcd_env == 2 && transposed ? 1 : xcd_env;
-  const unsigned slabs = (unsigned)(p.cout / 64);
-  const dim3 grid(p.w_xcd == 2 && slabs <= 8 && (slabs & (slabs - 1)) == 0 ? (tiles + 7u) / 8u * 8u : tiles, slabs, 1);
   const bool cat = p.c_b > 0;
   const int ar = (p.arith == kArF32 || p.arith == kArBf16x3) ? p.arith : (p.a_split ? kArF16x2Pre : kArF16x2);
-#define IMF_W_LAUNCH(AR)                                                    \
-  do {                                                                      \
-    if (use == 1 && waves == 8 && !cat) {                                   \
-      k_spconv_w<false, 8, AR, 1><<<grid, 512, 0, st>>>(p);                 \
-    } else if (waves == 8) {                                                \
-      if (cat) k_spconv_w<true, 8, AR><<<grid, 512, 0, st>>>(p);            \
-      else     k_spconv_w<false, 8, AR><<<grid, 512, 0, st>>>(p);           \
-    } else {                                                                \
-      if (cat) k_spconv_w<true, 4, AR><<<grid, 256, 0, st>>>(p);            \
-      else     k_spconv_w<false, 4, AR><<<grid, 256, 0, st>>>(p);           \
-    }                                                                       \
-  } while (0)
-  if (ar == kArF32 && !u48) IMF_W_LAUNCH(kArF32);
-  else if (half8) {
-    if (cat) k_spconv_w<true, 8, kArBf16x3, 0, 2, 4><<<grid, 512, 0, st>>>(p);
-    else     k_spconv_w<false, 8, kArBf16x3, 0, 2, 4><<<grid, 512, 0, st>>>(p);
-  }
-  else if (half && occ_bit) {                        // half tiles under the four-wavefronts-per-SIMD budget (127 VGPRs, 25 KiB)
-    if (cat) k_spconv_w<true, 4, kArBf16x3, 0, 2, 4><<<grid, 256, 0, st>>>(p);
-    else     k_spconv_w<false, 4, kArBf16x3, 0, 2, 4><<<grid, 256, 0, st>>>(p);
-  }
-  else if (half) {
-    if (cat) k_spconv_w<true, 4, kArBf16x3, 0, 2><<<grid, 256, 0, st>>>(p);
-    else     k_spconv_w<false, 4, kArBf16x3, 0, 2><<<grid, 256, 0, st>>>(p);
-  }
-  else if (u48) {
-#define IMF_W_LAUNCH_U(AR)                                                  \
-  do {                                                                      \
-    if (cat) k_spconv_w<true, 8, AR, 0, 3><<<grid, 512, 0, st>>>(p);        \
-    else     k_spconv_w<false, 8, AR, 0, 3><<<grid, 512, 0, st>>>(p);       \
-  } while (0)
-    if (ar == kArF32) IMF_W_LAUNCH_U(kArF32);
-    else if (ar == kArBf16x3 && waves == 4) {
-      if (cat) k_spconv_w<true, 4, kArBf16x3, 0, 3><<<grid, 256, 0, st>>>(p);
-      else     k_spconv_w<false, 4, kArBf16x3, 0, 3><<<grid, 256, 0, st>>>(p);
-    }
-    else if (ar == kArBf16x3) IMF_W_LAUNCH_U(kArBf16x3);
-    else if (ar == kArF16x2Pre) IMF_W_LAUNCH_U(kArF16x2Pre);
-    else IMF_W_LAUNCH_U(kArF16x2);
-#undef IMF_W_LAUNCH_U
-  }
-  else if (occ3) {
-    if (cat) k_spconv_w<true, 4, kArBf16x3, 0, 4, 3><<<grid, 256, 0, st>>>(p);
-    else     k_spconv_w<false, 4, kArBf16x3, 0, 4, 3><<<grid, 256, 0, st>>>(p);
-  }
-  else if (ar == kArBf16x3) IMF_W_LAUNCH(kArBf16x3);
-  else if (ar == kArF16x2Pre) IMF_W_LAUNCH(kArF16x2Pre);
-  else IMF_W_LAUNCH(kArF16x2);
-#undef IMF_W_LAUNCH
+  const WBuild b = w_build_of(tag, ar, cat, tiles);
+  // Workgroup order: slab by XCD and one range of consecutive units per XCD (the XCD's L2 serves a fraction of the input
+  // rows).  A transposed map's tiles are grouped by parity class -- consecutive tiles there are not neighbours in space --
+  // so it keeps slab by XCD with the tiles interleaved.  Measurements: LAB_NOTES.md 4h-i.
+  const bool transposed = p.n_slots != (p.n_out + IMF_TILE_ROWS - 1) / IMF_TILE_ROWS * IMF_TILE_ROWS;
+  p.w_xcd = transposed ? 1 : 2;
+  const unsigned slabs = (unsigned)(p.cout / 64);
+  const dim3 grid(p.w_xcd == 2 && slabs <= 8 && (slabs & (slabs - 1)) == 0 ? (b.units + 7u) / 8u * 8u : b.units, slabs, 1);
+  if (ar == kArF32) launch_w_build<kArF32>(b, cat, grid, st, p);
+  else if (ar == kArBf16x3) launch_w_build<kArBf16x3>(b, cat, grid, st, p);
+  else if (ar == kArF16x2Pre) launch_w_build<kArF16x2Pre>(b, cat, grid, st, p);
+  else launch_w_build<kArF16x2>(b, cat, grid, st, p);
 }
 
 }  // namespace imf

@@ -426,29 +426,34 @@ def pack_weights(kernel, out=None, split16=False, variant=None):
     return packed
 
 
-# variant 6 runs k_spconv_g (operands staged by LDS-DMA, csrc/spconv_g.hip) unless IMF_H3_GLDS=0 or the call asks
-# for the register-staged k_spconv_h3 (`staging="regs"`, kernel_tag bit 1); the two agree bit for bit
-H3_DMA = int(os.environ.get("IMF_H3_GLDS", "1")) != 0
+# `staging` of spconv -> imf_conv_args.kernel_tag (IMF_TAG_* of include/imfnet_hip.h say what each bit selects)
+STAGING_TAGS = {
+    None: 0, "dma": 0,                                   # the library default: the LDS-DMA kernel k_spconv_g
+    "regs": _lib.TAG_REGS,                               # variant 0: the register-staged k_spconv_mfma
+    "wave8": _lib.TAG_WAVE8, "wave4": _lib.TAG_WAVE4,    # the wave-split kernel k_spconv_w, whole tiles
+    "wave8u": _lib.TAG_WAVE8 | _lib.TAG_U48, "wave4u": _lib.TAG_WAVE4 | _lib.TAG_U48,                   # 48-row units
+    "wave4h": _lib.TAG_WAVE4 | _lib.TAG_HALF,                                                           # half tiles (bf16x3)
+    "wave4o": _lib.TAG_WAVE4 | _lib.TAG_OCC,             # bf16x3: the builds for one more wavefront per SIMD
+    "wave4h4": _lib.TAG_WAVE4 | _lib.TAG_HALF | _lib.TAG_OCC, "wave8h4": _lib.TAG_WAVE8 | _lib.TAG_HALF | _lib.TAG_OCC,
+}
+_WAVE = _lib.TAG_WAVE8 | _lib.TAG_WAVE4
 
 
 def conv_kernel_name(variant, cin, cout, staging=None, kernel_tag=0):
     """Label of the kernel family a launch runs on (bench.py groups by it).  Variant 0 (fp32 MFMA) runs on the LDS-DMA
     kernels too since round 5 (AR = kArF32, csrc/spconv_g.hip / spconv_w.hip): same family names with an `/f32` suffix;
-    kernel_tag bit 1 / staging="regs" selects round 1's register-staged k_spconv_mfma."""
-    if kernel_tag & 16:
+    TAG_REGS / staging="regs" selects the register-staged k_spconv_mfma.  The strings are a recorded contract
+    (tests/golden/conv_kernel_names.json) -- including that a `staging` name other than "wave8" reads `k_spconv_w<4>`."""
+    if kernel_tag & _lib.TAG_HEAD:
         return "k_pointwise_head_b3" if variant == 3 else "k_pointwise_head"
+    tag = kernel_tag | STAGING_TAGS.get(staging, 0)
+    cb = 4 if cout % 64 == 0 else 2
+    if variant not in (0, 3, 6) or (variant == 0 and tag & _lib.TAG_REGS):
+        return f"k_spconv_mfma<{cb},{4 if cin % 64 == 0 else 2}>"
     suffix = {0: "/f32", 3: "/b3"}.get(variant, "")
-    regs0 = variant == 0 and (kernel_tag & 2 or staging == "regs")
-    if variant in (0, 3, 6) and not regs0 and (kernel_tag & 12 or staging in ("wave8", "wave4", "wave4h", "wave8u", "wave4u", "wave4o", "wave4h4", "wave8h4")):
-        return f"k_spconv_w<{8 if (kernel_tag & 4 or staging == 'wave8') else 4}>" + suffix
-    if variant == 3:
-        return f"k_spconv_g<{4 if cout % 64 == 0 else 2}, 0>" + suffix
-    if variant == 6:
-        dma = H3_DMA if staging is None else staging == "dma"
-        return f"k_spconv_{'g' if dma else 'h3'}<{4 if cout % 64 == 0 else 2}, 0>"
-    if variant == 0 and not regs0:
-        return f"k_spconv_g<{4 if cout % 64 == 0 else 2}, 0>" + suffix
-    return f"k_spconv_mfma<{4 if cout % 64 == 0 else 2},{4 if cin % 64 == 0 else 2}>"
+    if tag & _WAVE:
+        return f"k_spconv_w<{8 if (kernel_tag & _lib.TAG_WAVE8 or staging == 'wave8') else 4}>" + suffix
+    return f"k_spconv_g<{cb}, 0>" + suffix
 
 
 FMT_A_SPLIT, FMT_RES_SPLIT, FMT_OUT_SPLIT = 1, 2, 4      # imf_conv_args.operand_format (include/imfnet_hip.h)
@@ -479,10 +484,11 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     """out[o] = epilogue(sum_k in[nbr[k][o]] @ W[k]) -- imf_spconv_fwd.  `operand_format` (variant 6, unsplit): FMT_A_SPLIT
     | FMT_RES_SPLIT | FMT_OUT_SPLIT -- which of in_a / in_b, residual, out are split-f16 operand images
     (`to_operand_image`) instead of fp32 rows.  `flags`: optional int32[1] device word that
-    receives IMF_FLAG_RANGE (32) when an output is NaN or >= 65504 in magnitude.  `staging` (variant 6): None = the
-    library default (LDS-DMA kernel k_spconv_g), "wave8" / "wave4" = the wave-split kernel for coarse levels
-    (csrc/spconv_w.hip; kvol > 1, cout % 64 == 0, no split-K); "regs" = the register-staged k_spconv_h3, which exists in
-    diagnostic builds of the library only (IMF_LIB=.../libimfnet_hip_h3.so; the product answers IMF_EUNSUPPORTED)."""
+    receives IMF_FLAG_RANGE (32) when an output is NaN or >= 65504 in magnitude.  `staging`: a key of STAGING_TAGS --
+    None / "dma" = the library default (LDS-DMA kernel k_spconv_g), "wave*" = a workgroup shape of the wave-split kernel
+    for coarse levels (csrc/spconv_w.hip; kvol > 1, cout % 64 == 0, no split-K); "regs" = variant 0's register-staged
+    k_spconv_mfma (variants 6 / 3 have none: IMF_EUNSUPPORTED / IMF_EINVAL).  `fused_reduce` (variant 0, split_k > 1):
+    the in-launch split-K combine of that kernel."""
     _req(in_a, torch.float32, "in_a", 2)
     if in_b is not None:
         _req(in_b, torch.float32, "in_b", 2)
@@ -499,16 +505,16 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     a.out = out.data_ptr()
     L = _lib.lib()
     split = 1 if variant == 1 else (int(split_k) if split_k else L.imf_spconv_auto_split(rb.n_slots, cout, rb.max_active))
-    if rb.kvol == 1 or staging in ("wave8", "wave4", "wave4h", "wave8u", "wave4u", "wave4o", "wave4h4", "wave8h4"):
+    if staging not in STAGING_TAGS:
+        raise ImfError(f"spconv: staging={staging!r}")
+    a.kernel_tag = STAGING_TAGS[staging]
+    if rb.kvol == 1 or a.kernel_tag & _WAVE:
         split = 1
     a.split_k, a.variant = split, int(variant)
     a.operand_format = int(operand_format)
     a.dyn_err = None if flags is None else flags.data_ptr()
-    if staging not in (None, "dma", "regs", "wave8", "wave4", "wave4h", "wave8u", "wave4u", "wave4o", "wave4h4", "wave8h4"):
-        raise ImfError(f"spconv: staging={staging!r}")
-    a.kernel_tag = {"regs": 2, "wave8": 4, "wave4": 8, "wave4h": 8 | 64, "wave8u": 4 | 128, "wave4u": 8 | 128, "wave4o": 8 | 256, "wave4h4": 8 | 64 | 256, "wave8h4": 4 | 64 | 256}.get(staging, 0)
     ws = None
-    nbytes = L.imf_spconv_workspace_bytes(rb.n_slots, cout, split)   # split-K partials / balanced-tail partials
+    nbytes = L.imf_spconv_workspace_bytes(rb.n_slots, cout, split)   # split-K partials
     if nbytes:
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=in_a.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
@@ -520,7 +526,7 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     if variant in (6, 3) and big:
         raise ImfError("variants 6 / 3 address their inputs through a 2 GiB buffer window: use variant 0 for larger matrices")
     if variant == 0 and big:
-        a.kernel_tag = 2                                  # the LDS-DMA kernels share that window: the register-staged kernel
+        a.kernel_tag = _lib.TAG_REGS                      # the LDS-DMA kernels share that window: the register-staged kernel
     need = (L.imf_packed_weight_floats_split16 if variant == 6 else L.imf_packed_weight_floats_bf16x3 if variant == 3
             else L.imf_packed_weight_floats)(rb.kvol, a.c_a + a.c_b, cout)
     if w_packed.numel() != need:

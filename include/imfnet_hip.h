@@ -261,7 +261,7 @@ typedef struct imf_conv_args {
   int32_t variant;        /* 0 = fp32 MFMA (v_mfma_f32_16x16x4_f32: the reference's arithmetic), since round 5 on the LDS-DMA
                                  kernels k_spconv_g / k_spconv_w (AR = kArF32) wherever their tables cover the shape
                                  (kvol <= 27, kvol * cin / 32 < 224, <= 1024 channels per source, inputs < 2 GiB), else --
-                                 or with kernel_tag bit 1 / `tickets` -- on round 1's register-staged k_spconv_mfma;
+                                 or with IMF_TAG_REGS / `tickets` -- on the register-staged k_spconv_mfma;
                              1 = the same arithmetic without any pipeline (simple reference kernel; any kvol);
                              2, 4, 5 = retired round-1 experiments (their measurements: DESIGN.md 4), IMF_EINVAL;
                              3 = "bf16x3": fp32 operands carried exactly by three bf16 parts each, six
@@ -269,15 +269,15 @@ typedef struct imf_conv_args {
                                  imf_pack_weights_bf16x3; fp32 rows in, fp32 rows out, no range restriction; kvol <= 27;
                                  in_a / in_b smaller than 2 GiB each).  k_spconv_g / k_spconv_w with AR = kArBf16x3;
                              6 = fp32-class arithmetic on the f16 matrix pipe with split operands, both operands staged
-                                 global -> LDS by DMA (k_spconv_g; see kernel_tag for the register-staged twin)
+                                 global -> LDS by DMA (k_spconv_g / k_spconv_w)
                                  (w_packed from imf_pack_weights_split16; kvol <= 27; |input| < 65504;
                                  in_a / in_b smaller than 2 GiB each: raw-buffer addressing) */
   void *workspace;        /* split-K partial sums (NULL allowed iff split_k resolves to 1) */
   size_t workspace_bytes; /* >= imf_spconv_workspace_bytes(n_slots, cout, split)                  */
   int32_t *tickets;       /* optional: int32[n_tiles * n_slabs] arrival counters, ZERO on entry (left zero on
                              exit): with split_k > 1 the last partition to finish a tile reduces it inside
-                             the same launch (agent-scope release/acquire) -- no second kernel.  Variant 0; with
-                             variant 6 in diagnostic builds only (measured slower than the second launch) */
+                             the same launch (agent-scope release/acquire) -- no second kernel.  Variant 0 only (its
+                             register-staged kernel k_spconv_mfma); variants 6 / 3 answer IMF_EUNSUPPORTED */
   void *ev_begin, *ev_end; /* optional hipEvent_t pair recorded on `stream` immediately around the
                               main MFMA kernel (not the split-K reduce): live roofline timing     */
   /* Capacity mode (variant 6; variant 0 with split_k == 1), for launch sequences captured once and replayed on fragments of different
@@ -290,29 +290,7 @@ typedef struct imf_conv_args {
    * imf_rulebook_transpose's parity classes, else 0). */
   const int32_t *n_out_dev;
   int32_t dyn_split_kvol, slots_extra;
-  int32_t kernel_tag;     /* variants 6, 3 and 0.  bit 0: profiling label -- the identical kernel under a second symbol
-                             (k_spconv_g<.., 1>: the image branch's dense convolutions).  bit 1: the register-staged twin
-                             k_spconv_h3 (csrc/spconv_h3.hip; same sums bit for bit) -- DIAGNOSTIC builds only (make h3 /
-                             stamps): the product library answers IMF_EUNSUPPORTED, as it does for variant 6 + `tickets`;
-                             with variant 0: round 1's register-staged fp32 kernel k_spconv_mfma (always built).
-                             bit 2 (4) / bit 3 (8): the wave-split kernel k_spconv_w (csrc/spconv_w.hip) with 8 / 4
-                             wavefronts per workgroup -- for levels of a few hundred 64-row tiles or fewer: one workgroup
-                             owns a (tile, 64-column slab) for all kernel offsets, its wavefronts split the tile's
-                             (offset, 32-channel chunk) list into contiguous ranges and combine their partial tiles through
-                             LDS in wavefront order, epilogue in the same launch.  Needs kvol > 1, cout % 64 == 0,
-                             split_k <= 1.  The wavefront count is part of the summation order (deterministic; a tile's
-                             sums do not depend on the row count, so exact and capacity mode agree bit for bit).
-                             bit 6 (64), with bit 3 and variant 3 only: HALF-TILE workgroups -- each 4-wavefront workgroup
-                             owns 32 of a tile's 64 rows (same offset list, same per-row sums as bit 3 alone): twice the
-                             workgroups for levels that leave CUs idle (one fragment per forward).
-                             bit 7 (128), with bit 2 (any variant) or bit 3 (variant 3): 48-ROW UNITS -- each workgroup owns
-                             slots 48 u .. 48 u + 47 whatever the tile boundaries and walks the union of the offset lists
-                             of the tiles it touches (8 wavefronts: a pair's stride-8 level, 184 workgroups instead of 136;
-                             4 wavefronts: the 64 -> 64 layers of level 0, three workgroups per CU).
-                             bit 8 (256), with bit 3 and variant 3: the build for one more wavefront per SIMD -- whole tiles
-                             for three (168 VGPRs), with bit 6 half tiles for four (127 VGPRs, 25 KiB of LDS; also with bit 2: half tiles of
-                             8 wavefronts, two workgroups per CU); the same
-                             sums as without the bit, bit for bit */
+  int32_t kernel_tag;     /* variants 6, 3 and 0: IMF_TAG_* bits (below) -- which kernel and workgroup shape; 0 = k_spconv_g */
   int32_t *dyn_err;       /* optional device flag word (any mode): IMF_FLAG_SPLIT_COVER when the rule asks for more
                              partitions than split_k covers; IMF_FLAG_RANGE when an OUTPUT value is NaN or |y| >= 65504,
                              i.e. cannot be an operand of a following variant-6 convolution */
@@ -331,6 +309,30 @@ typedef struct imf_conv_args {
                              its consumers the conversions (same products bit for bit).  A residual read takes hi + lo,
                              i.e. the value to 22 significant bits (relative 2^-22). */
 } imf_conv_args;
+/* imf_conv_args.kernel_tag (variants 6, 3 and 0): which kernel and which workgroup shape a launch takes.  The values are
+ * part of the ABI (trace records and C callers carry them as integers).  Bits that do not apply to a launch's arithmetic
+ * are ignored (csrc/spconv_w.hip, w_build_of, says which).  Whatever the bits, a row's sums depend on the wavefront
+ * count and the unit shape only, never on the row count: exact and capacity mode agree bit for bit. */
+#define IMF_TAG_LABEL   1   /* profiling label: the identical kernel under a second symbol (k_spconv_g<.., 1>, whole-tile
+                               k_spconv_w of 8 wavefronts: the image branch's dense convolutions) */
+#define IMF_TAG_REGS    2   /* variant 0: the register-staged fp32 kernel k_spconv_mfma (also taken with `tickets`; the one
+                               that serves inputs beyond the 2 GiB buffer window); variants 6 / 3: IMF_EUNSUPPORTED */
+#define IMF_TAG_WAVE8   4   /* the wave-split kernel k_spconv_w (csrc/spconv_w.hip) with 8 wavefronts per workgroup ... */
+#define IMF_TAG_WAVE4   8   /* ... or with 4 (WAVE8 wins when both are set) -- for levels of a few hundred 64-row tiles or
+                               fewer: one workgroup owns a (unit of rows, 64-column slab) for all kernel offsets, its
+                               wavefronts split the (offset, 32-channel chunk) list into contiguous ranges and combine
+                               their partial tiles through LDS in wavefront order, epilogue in the same launch.  Needs
+                               cout % 64 == 0, kvol > 1 or cin >= 256, split_k <= 1, no tickets */
+#define IMF_TAG_HEAD   16   /* trace label of the fused pointwise head (imf_net_trace.kernel_tag only; not a launch shape) */
+#define IMF_TAG_HALF   64   /* with WAVE4, variant 3 (with OCC also WAVE8): HALF-TILE workgroups -- 32 of a tile's 64 rows
+                               each, same offset list and per-row sums: twice the workgroups for levels that leave CUs idle */
+#define IMF_TAG_U48   128   /* with WAVE8 (any variant) or WAVE4 (variant 3), not with HALF: 48-ROW UNITS -- a workgroup owns
+                               slots 48 u .. 48 u + 47 whatever the tile boundaries and walks the union of the offset lists
+                               of the tiles it touches */
+#define IMF_TAG_OCC   256   /* variant 3: the build for one more wavefront per SIMD -- with WAVE4 whole tiles for three
+                               (168 VGPRs), with HALF half tiles for four (127 VGPRs, 25 KiB of LDS; WAVE4 or WAVE8); the
+                               same sums as without the bit, bit for bit */
+
 #define IMF_FMT_A_SPLIT   1
 #define IMF_FMT_RES_SPLIT 2
 #define IMF_FMT_OUT_SPLIT 4
@@ -576,11 +578,11 @@ typedef struct imf_net_trace {         /* optional per-convolution measurement r
 /* Which LDS-DMA kernel (variants 3, 6 and 0 alike: the arithmetic is a template argument of the same two kernels) the
  * ResUNet executors (imf_resunet_forward, imf_fragment_forward and the Python plan that mirrors them) use for a convolution whose OUTPUT rows live on pyramid level `level` (0 = tensor stride 1):
  * the value for imf_conv_args.kernel_tag.  Level 0 (thousands of 64-row tiles): k_spconv_g, unsplit (variant 3: the
- * wave-split kernel with 4 wavefronts and 48-row units, kernel_tag 8 | 128, for the 64 -> 64 layers; with half tiles,
- * 8 | 64 | 256, for the 128 -> 64 up-convolution).  Level 1: the
- * wave-split kernel with 4 wavefronts per workgroup (kernel_tag 8; variant 3: 8 | 256); levels 2 and 3: with 8 (kernel_tag 4); variant 3 with
- * ONE fragment in the forward (n_items == 1): half-tile workgroups of 4 wavefronts (8 | 64 | 256) on level 1 and of 8 (4 | 64 | 256) on levels 2-3; every variant
- * with two or more fragments: 48-row units (4 | 128) on level 3, and from three fragments on 4 wavefronts on level 2.  The choice is
+ * wave-split kernel with 4 wavefronts and 48-row units, IMF_TAG_WAVE4 | IMF_TAG_U48, for the 64 -> 64 layers; with half tiles,
+ * WAVE4 | HALF | OCC, for the 128 -> 64 up-convolution).  Level 1: the
+ * wave-split kernel with 4 wavefronts per workgroup (WAVE4; variant 3: WAVE4 | OCC); levels 2 and 3: with 8 (WAVE8); variant 3 with
+ * ONE fragment in the forward (n_items == 1): half-tile workgroups of 4 wavefronts (WAVE4 | HALF | OCC) on level 1 and of 8 (WAVE8 | HALF | OCC) on levels 2-3; every variant
+ * with two or more fragments: 48-row units (WAVE8 | U48) on level 3, and from three fragments on 4 wavefronts on level 2.  The choice is
  * a function of the LEVEL, the layer's channel counts and the batch size only -- never of the row count -- so exact mode,
  * capacity mode and a graph replay form every sum in the
  * same order (bit-identical descriptors) without a device-side split rule.  What DOES depend on n_items is the partition of a

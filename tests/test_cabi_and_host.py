@@ -66,6 +66,45 @@ def test_kernel_policy_is_static_per_layer_and_batch():
     assert tag(2, 27, 64, 64, 1, 2) == 0                                                 # other variants: no wave-split kernel
 
 
+def test_kernel_tag_names_mirror_the_header():
+    """The IMF_TAG_* constants of include/imfnet_hip.h, their mirror in _lib and the staging table of ops: the values are
+    part of the ABI (bench.py reads 64 and 128 from trace records, C callers pass integers), so they are pinned here."""
+    from imfnet_amd import _lib, ops
+    text = open(os.path.join(ROOT, "include", "imfnet_hip.h")).read()
+    header = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define IMF_TAG_(\w+)\s+(\d+)\b", text, flags=re.M)}
+    assert header == {"LABEL": 1, "REGS": 2, "WAVE8": 4, "WAVE4": 8, "HEAD": 16, "HALF": 64, "U48": 128, "OCC": 256}
+    mirror = {k[4:]: v for k, v in vars(_lib).items() if k.startswith("TAG_")}
+    assert mirror == header
+    assert ops.STAGING_TAGS == {None: 0, "dma": 0, "regs": 2, "wave8": 4, "wave4": 8, "wave4h": 8 | 64, "wave8u": 4 | 128,
+                                "wave4u": 8 | 128, "wave4o": 8 | 256, "wave4h4": 8 | 64 | 256, "wave8h4": 4 | 64 | 256}
+    tag = _lib.lib().imf_resunet_conv_kernel_tag                     # the policy, spelled with the names
+    assert tag(3, 27, 256, 256, 3, 2) == _lib.TAG_WAVE8 | _lib.TAG_U48
+    assert tag(0, 27, 64, 64, 3, 2) == _lib.TAG_WAVE4 | _lib.TAG_U48
+    assert tag(0, 27, 128, 64, 3, 2) == _lib.TAG_WAVE4 | _lib.TAG_HALF | _lib.TAG_OCC
+    assert tag(2, 27, 128, 128, 3, 1) == _lib.TAG_WAVE8 | _lib.TAG_HALF | _lib.TAG_OCC
+    assert tag(1, 27, 64, 64, 3, 2) == _lib.TAG_WAVE4 | _lib.TAG_OCC and tag(1, 27, 64, 64, 6, 2) == _lib.TAG_WAVE4
+
+
+def test_conv_kernel_name_matches_the_recorded_table():
+    """ops.conv_kernel_name (bench.py groups kernels by its strings) over variant x cout x cin x every kernel_tag the
+    policy, the image / fusion branches, the head's trace record or a staging name can produce, plus every staging name,
+    against the strings recorded before the launch shape got names (tests/golden/conv_kernel_names.json).  Left out: variant 6
+    with staging "regs" -- it named the retired register-staged split-f16 kernel and cannot be launched."""
+    import itertools
+    from imfnet_amd import ops
+    table = json.load(open(os.path.join(GOLDEN, "conv_kernel_names.json")))
+    assert table["columns"] == ["variant", "cin", "cout", "staging", "kernel_tag", "name"]
+    want = {tuple(r[:5]): r[5] for r in table["rows"]}
+    tags = sorted({0, 1, 2, 4, 5, 8, 16, 8 | 64, 8 | 128, 4 | 128, 8 | 256, 8 | 64 | 256, 4 | 64 | 256} | set(ops.STAGING_TAGS.values()))
+    keys = []
+    for v, cout, cin in itertools.product((0, 1, 3, 6), (32, 64, 128), (32, 64, 96)):
+        keys += [(v, cin, cout, None, t) for t in tags]
+        keys += [(v, cin, cout, s, 0) for s in ops.STAGING_TAGS if s is not None and not (v == 6 and s == "regs")]
+    assert set(keys) == set(want) and len(keys) == len(want) == 819
+    for v, cin, cout, s, t in keys:
+        assert ops.conv_kernel_name(v, cin, cout, staging=s, kernel_tag=t) == want[(v, cin, cout, s, t)], (v, cin, cout, s, t)
+
+
 def test_conv_args_struct_matches_header_layout():
     """ctypes mirror of struct imf_conv_args: field order / count tracks the header."""
     from imfnet_amd._lib import ConvArgs

@@ -201,7 +201,7 @@ def test_spconv_matches_oracle(ops, geom_s5, ca, cb, cout, which, mode):
           "b3_wave8h4": {"variant": 3, "staging": "wave8h4"},          # ... of eight wavefronts (a single fragment's coarse levels)
           "h3": {"variant": 6},
           "h3_split1": {"variant": 6, "split_k": 1}, "h3_split5": {"variant": 6, "split_k": 5},
-          # variant 6 = the LDS-DMA kernel k_spconv_g (the register-staged k_spconv_h3 lives in diagnostic builds only)
+          # variant 6 = the LDS-DMA kernel k_spconv_g
           # the wave-split kernel of the coarse levels (csrc/spconv_w.hip): whole tile per workgroup, 8 / 4 wavefronts
           "h3_wave8": {"variant": 6, "staging": "wave8"}, "h3_wave4": {"variant": 6, "staging": "wave4"}}[mode]
     if mode.endswith(("wave8", "wave4", "wave4h", "wave8u", "wave4u", "wave4o", "wave4h4", "wave8h4")) and (kvol == 1 or cout % 64):
@@ -701,8 +701,8 @@ def test_spconv_argument_errors(ops, geom_s5):
         with pytest.raises(ImfError):
             ops.spconv(f[:, :32].contiguous(), wp, 32, rb, variant=retired)
     wp6 = ops.pack_weights(torch.zeros(27, 32, 32, device=DEV), split16=True)
-    for kw in ({"staging": "regs"}, {"split_k": 4, "fused_reduce": True}):      # the register-staged twin: diagnostic builds only
-        with pytest.raises(ImfError, match="diagnostic"):
+    for kw in ({"staging": "regs"}, {"split_k": 4, "fused_reduce": True}):      # variant 6 has neither: IMF_EUNSUPPORTED
+        with pytest.raises(ImfError, match="variant 6 has no register-staged kernel"):
             ops.spconv(f[:, :32].contiguous(), wp6, 32, rb, variant=6, **kw)
 
 

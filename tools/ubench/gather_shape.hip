@@ -1,6 +1,6 @@
 // Micro-benchmark: what does the SHAPE of a row gather cost on the vector-memory path (TA / L1) of gfx950?
 //
-// The sparse convolution gathers 16 input rows x 128 bytes per wavefront and sub-stage.  k_spconv_h3 loads them in
+// The sparse convolution gathers 16 input rows x 128 bytes per wavefront and sub-stage.  The register-staged kernels load them in
 // MFMA-fragment shape (lane l: row l & 15, 16-byte piece l >> 4): four consecutive lanes touch four DIFFERENT rows,
 // i.e. every lane is its own L1 access.  The alternatives below let four (or eight) consecutive lanes read one
 // contiguous 64 (128) byte run of ONE row, which then needs a lane transpose (through LDS) before the MFMA.
