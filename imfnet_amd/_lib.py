@@ -217,6 +217,8 @@ SIGNATURES = {
     "imf_radius_count": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _P, _P, _Z, _P]),
     "imf_radius_pairs_workspace_bytes": (_Z, [_L, _L]),
     "imf_radius_pairs": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _L, _P, _P, _P, _Z, _P]),
+    "imf_robust_transform_workspace_bytes": (_Z, [_L]),
+    "imf_robust_transform": (_I, [_P, _P, _P, _L, _P, _P, _P, _Z, _P]),
     "imf_hash_capacity": (_L, [_L]),
     "imf_unique_workspace_bytes": (_Z, [_L]),
     "imf_voxelize": (_I, [_P, _I, _L, _D, _I, _P, _P, _P, _P, _L, _P, _P, _P]),

@@ -247,3 +247,45 @@ def radius_pairs(src, dst, T=None, r=None, device="cuda", capacity=None):
     if total > cap:
         pairs, offsets, total, err = radius_pairs_call(s, d, Th, r, total)
     return pairs[:total], offsets
+
+
+def robust_transform_device(p0, p1, weight=None):
+    """One imf_robust_transform launch on device fp64 tensors [n, 3] (weight: device fp64 [n] or None).  Returns the
+    device buffer of 136 bytes: 16 doubles of T (row-major 4x4), then the int32 flag.  No host synchronisation."""
+    for name, t in (("pts0", p0), ("pts1", p1)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 3
+                and t.is_contiguous()):
+            raise ImfError(f"robust_transform_device: {name} must be a contiguous CUDA float64 [n, 3] tensor")
+    if p1.shape != p0.shape or p1.device != p0.device:
+        raise ImfError(f"robust_transform_device: pts0 {tuple(p0.shape)} on {p0.device}, pts1 {tuple(p1.shape)} on {p1.device}")
+    if weight is not None and not (torch.is_tensor(weight) and weight.device == p0.device and weight.is_contiguous()
+                                   and weight.dtype == torch.float64 and weight.shape == (p0.shape[0],)):
+        raise ImfError(f"robust_transform_device: weight must be a contiguous float64 [{p0.shape[0]}] tensor on {p0.device}")
+    L = _lib.lib()
+    n, dev = p0.shape[0], p0.device
+    nbytes = L.imf_robust_transform_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    out = torch.empty(136, dtype=torch.uint8, device=dev)
+    check(L.imf_robust_transform(p0.data_ptr() if n else None, p1.data_ptr() if n else None,
+                                 weight.data_ptr() if weight is not None and n else None, n, out.data_ptr(),
+                                 out[128:].data_ptr(), ws.data_ptr() if ws is not None else None, nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream), "imf_robust_transform")
+    return out
+
+
+def robust_transform(pts0, pts1, weight=None, device="cuda"):
+    """util/transform_estimation.py:89-116 est_quad_linear_robust(pts0, pts1, weight) on the device, in fp64
+    (imf_robust_transform; the loop is restated in csrc/robust.hip): the transform that takes pts0 [n, 3] onto its
+    correspondences pts1 [n, 3] after 20 reweighted rounds.  Returns (T float64 4x4 numpy, ok); ok is False and T the
+    identity when a round's system could not be solved (upstream raises).  One device-to-host copy per call."""
+    p0 = _pair_points(pts0, device, "pts0")
+    p1 = _pair_points(pts1, p0.device, "pts1")
+    if p0.shape != p1.shape:
+        raise ImfError(f"robust_transform: pts0 {tuple(p0.shape)} and pts1 {tuple(p1.shape)} differ")
+    w = None
+    if weight is not None:
+        w = torch.as_tensor(weight).to(device=p0.device, dtype=torch.float64).reshape(-1).contiguous()
+        if w.shape[0] != p0.shape[0]:
+            raise ImfError(f"robust_transform: {w.shape[0]} weights for {p0.shape[0]} pairs")
+    raw = robust_transform_device(p0, p1, w).cpu().numpy()
+    return raw[:128].view(np.float64).reshape(4, 4).copy(), not bool(raw[128:].view(np.int32)[0])

@@ -1,5 +1,5 @@
-"""The 3DMatch training pairs: IndoorPairDataset (lib/data_loaders.py:244-345), sample_random_trans (:95-101),
-Jitter (lib/transforms.py:18-30) and collate_pair_fn (:23-84).
+"""The training pairs: IndoorPairDataset (3DMatch, lib/data_loaders.py:244-345) and KITTINMPairDataset (KITTI odometry,
+:500-714), sample_random_trans (:95-101), Jitter (lib/transforms.py:18-30) and collate_pair_fn (:23-84).
 
 An item is made in two halves.  `load(idx)` decodes the two PLY files and images on the host; it touches no GPU and
 runs on the trainer's decode threads.  `prepare(raw)` runs in the trainer's process on its current stream: random
@@ -9,6 +9,7 @@ the dataset's own `numpy.random.Generator`, in the order scale, rotation T0, rot
 mixes `random`, `np.random` and a RandomState and cannot be replayed.
 """
 import glob
+import logging
 import os
 
 import numpy as np
@@ -16,6 +17,8 @@ import torch
 from scipy.linalg import expm
 
 from ..dataio import process_image, read_image, read_ply_points
+
+LOG = logging.getLogger("imfnet_amd.train")
 
 
 def M(axis, theta):
@@ -143,6 +146,103 @@ class IndoorPairDataset:
             feats.append(torch.from_numpy(f.astype(np.float32)).to(dev))
         return dict(xyz0=v0, xyz1=v1, coords0=lv0.coords[:, 1:], coords1=lv1.coords[:, 1:], feats0=feats[0],
                     feats1=feats[1], matches=matches, trans=trans, search_radius=r, image0=image0, image1=image1)
+
+    def __getitem__(self, idx):
+        return self.prepare(self.load(idx))
+
+
+class KITTINMPairDataset:
+    """The KITTI odometry pairs (lib/data_loaders.py:626-714 for the pair list, :500-623 for an item; IS_ODOMETRY),
+    train and val phases, with IndoorPairDataset's item dict and load / prepare split.  `sequences`: the odometry
+    sequence numbers of the phase (config/train_kitti.txt, val_kitti.txt).  `config` needs kitti_root, voxel_size,
+    positive_pair_search_voxel_size_multiplier, min_scale, max_scale, use_random_scale, image_H, image_W and may carry
+    own_image.
+
+    Kept: the pair list (kitti.pairs_of_sequence per sequence, minus kitti.DROPPED_PAIRS); the ground truth through
+    the `<kitti_root>/icp` cache shared with the evaluator (kitti.ground_truth: pose algebra, then the GPU ICP on 5 cm
+    voxels); no random rotation in any phase (upstream forces it off for the odometry layout); the random scale of
+    the train phase on the float32 scan and the search radius (probability 0.95, a factor in [min_scale, max_scale]);
+    the float32-quotient first-occurrence voxels (kitti.voxelize_f32); ones as features, with Jitter in the train
+    phase; both images read from frame t0 unless own_image.
+    Changed: a drawn scale also multiplies the translation of `trans` (upstream leaves the matrix as it is, so a scaled
+    pair's points and ground truth disagree by (1 - scale) t, metres on KITTI); a pair with fewer than
+    kitti.MIN_MATCHES positive pairs is logged and `prepare` returns None (upstream raises ValueError and the epoch
+    ends); the draws come from the data set's own Generator in the order scale coin, scale, jitter 0, jitter 1."""
+    quantize = "f32"                       # the trainer voxelises the representatives as the loader did
+
+    def __init__(self, phase, sequences, config, seed=0, device="cuda"):
+        from .. import kitti as K
+        self.phase, self.config = phase, config
+        self.root = config.kitti_root
+        self.own_image = bool(getattr(config, "own_image", False))
+        self.positions = {d: K.read_poses(self.root, d) for d in sequences}
+        self.files = K.pair_list(self.root, list(sequences))
+        train = phase in ("train", "trainval")
+        self.random_scale = train and bool(config.use_random_scale)
+        self.random_rotation = False
+        self.jitter = train
+        self.voxel_size = float(config.voxel_size)
+        self.matching_search_voxel_size = self.voxel_size * float(config.positive_pair_search_voxel_size_multiplier)
+        self.device = torch.device(device)
+        self.skipped = {}                  # (drive, t0, t1) -> positive pairs, of every pair `prepare` refused
+        self.reset_seed(seed)
+
+    def reset_seed(self, seed=0):
+        self.rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return len(self.files)
+
+    def load(self, idx):
+        """Host decode of pair idx: ((drive, t0, t1), xyz0, xyz1 float32 [N,3], image0, image1 float32 [3,H,W])."""
+        from .. import kitti as K
+        drive, t0, t1 = self.files[idx]
+        H, W = int(self.config.image_H), int(self.config.image_W)
+        f0, f1 = K.pair_image_paths(self.root, drive, t0, t1, self.own_image)
+        return ((drive, t0, t1), K.read_scan(K.velodyne_path(self.root, drive, t0)),
+                K.read_scan(K.velodyne_path(self.root, drive, t1)), K.load_image(f0, H, W)[0], K.load_image(f1, H, W)[0])
+
+    def prepare(self, raw, timings=None):
+        """Ground truth (cache or GPU ICP), scale, voxelisation and positive pairs on the GPU.  Returns
+        IndoorPairDataset.prepare's item dict plus `key` = (drive, t0, t1), or None for a pair with too few positive
+        pairs."""
+        from .. import kitti as K
+        from ..matching import radius_pairs
+        (drive, t0, t1), xyz0, xyz1, image0, image1 = raw
+        rng, dev = self.rng, self.device
+        r = self.matching_search_voxel_size
+        tk0 = _tick(timings, dev)
+        trans, _ = K.ground_truth(self.root, drive, t0, t1, xyz0, xyz1, self.positions[drive], dev)
+        if self.random_scale and rng.random() < 0.95:
+            scale = self.config.min_scale + (self.config.max_scale - self.config.min_scale) * rng.random()
+            r *= scale
+            xyz0, xyz1 = np.float32(scale) * xyz0, np.float32(scale) * xyz1
+            trans = trans.copy()
+            trans[:3, 3] *= float(np.float32(scale))
+        sides = []
+        for xyz in (xyz0, xyz1):
+            pts = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)).to(dev)
+            coords, first = K.voxelize_f32(pts, self.voxel_size)
+            sides.append((pts[first.long()].double(), coords[:, 1:].contiguous()))
+        (v0, c0), (v1, c1) = sides
+        tk1 = _tick(timings, dev)
+        matches, _ = radius_pairs(v0, v1, trans, r, device=dev)
+        tk2 = _tick(timings, dev)
+        if timings is not None:
+            timings["geometry"] = timings.get("geometry", 0.0) + tk1 - tk0
+            timings["pairs"] = timings.get("pairs", 0.0) + tk2 - tk1
+        if matches.shape[0] < K.MIN_MATCHES:
+            self.skipped[(drive, t0, t1)] = int(matches.shape[0])
+            LOG.warning(f"skipped pair {drive}, {t0}, {t1}: {matches.shape[0]} positive pairs (< {K.MIN_MATCHES})")
+            return None
+        feats = []
+        for n in (v0.shape[0], v1.shape[0]):
+            f = np.ones((n, 1))
+            if self.jitter and rng.random() < 0.95:                      # Jitter(mu=0, sigma=0.01)
+                f = f + rng.normal(0.0, 0.01, (n, 1))
+            feats.append(torch.from_numpy(f.astype(np.float32)).to(dev))
+        return dict(xyz0=v0, xyz1=v1, coords0=c0, coords1=c1, feats0=feats[0], feats1=feats[1], matches=matches,
+                    trans=trans, search_radius=r, image0=image0, image1=image1, key=(drive, t0, t1))
 
     def __getitem__(self, idx):
         return self.prepare(self.load(idx))

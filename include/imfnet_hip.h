@@ -858,6 +858,23 @@ int imf_radius_pairs(const double *src, int64_t n_src, const double *dst, int64_
                      int64_t *offsets, int32_t *pairs, int64_t capacity, int64_t *out_total, int32_t *out_err,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Robust transform from correspondences (the trainer's validation: RTE / RRE / success) ------------------------------
+ * imf_robust_transform replaces util/transform_estimation.py:89-116 est_quad_linear_robust(pts0, pts1, weight): 20
+ * rounds of the small-angle linear fit (3n x 6 system of the current points, normal equations, Rz Ry Rx and a
+ * translation from the six unknowns, points moved, T composed), every pair reweighted by par / (|p0 - p1| + par) with
+ * par = 1 halved at rounds 5, 10 and 15 (the loop restated in csrc/robust.hip).  pts0, pts1 [n,3] device fp64, row i
+ * of one corresponding to row i of the other; weight: device fp64 [n] for the first round, or NULL = ones.  Outputs
+ * (device): out_T 16 doubles (row-major 4x4, pts0 -> pts1), out_meta int32[1] = 1 when a round's system could not be
+ * solved (fewer than three usable rows, collinear points, a NaN or infinite input; upstream raises from torch.inverse),
+ * in which case out_T is the identity and the call still returns 0.  n == 0: the same flag and the identity, no kernel
+ * launched (pts0 / pts1 may be NULL).  ONE launch of one workgroup of 512 threads, no host synchronisation; fp64 throughout (upstream:
+ * float32), no floating-point atomics, a fixed summation order: bit-identical from run to run.  workspace:
+ * imf_robust_transform_workspace_bytes(n) bytes, 256-byte aligned; 0 (workspace may be NULL) while every thread's rows
+ * fit its registers, n <= 5120. */
+size_t imf_robust_transform_workspace_bytes(int64_t n);
+int imf_robust_transform(const double *pts0, const double *pts1, const double *weight, int64_t n, double *out_T,
+                         int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Training backward of the sparse convolution (last item) ---------------------------------------
  * Replaces: the backward of ME.MinkowskiConvolution / ConvolutionTranspose under loss.backward(), lib/trainer.py:495-569.
  * The INPUT gradient is imf_spconv_fwd itself over the opposite kernel map with transposed weights
