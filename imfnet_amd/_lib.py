@@ -140,6 +140,13 @@ class FragmentIO(C.Structure):
                 ("inputs_event", C.c_void_p), ("reuse_event", C.c_void_p)]
 
 
+class TsdfParams(C.Structure):
+    """struct imf_tsdf_params."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("voxel_length", C.c_double), ("sdf_trunc", C.c_double), ("depth_scale", C.c_double),
+                ("depth_trunc", C.c_double), ("lattice_offset", C.c_double), ("height", C.c_int32), ("width", C.c_int32)]
+
+
 class Job(C.Structure):
     """struct imf_job (one forward of the streaming pipeline)."""
     _fields_ = [("net", C.POINTER(ResunetDesc)), ("img", C.POINTER(ImageDesc)), ("caps", C.POINTER(FragmentCaps)),
@@ -163,6 +170,8 @@ SIGNATURES = {
     "imf_ply_read_points": (_L, [C.c_char_p, _P, _L]),
     "imf_png_info": (_I, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_png_read_f32": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "imf_png_read_u16": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "imf_ply_write_points": (_I, [C.c_char_p, _P, _L]),
     "imf_jpeg_info": (_I, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_jpeg_read_u8": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_resize_bilinear_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _I]),
@@ -219,6 +228,11 @@ SIGNATURES = {
     "imf_radius_pairs": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _L, _P, _P, _P, _Z, _P]),
     "imf_robust_transform_workspace_bytes": (_Z, [_L]),
     "imf_robust_transform": (_I, [_P, _P, _P, _L, _P, _P, _P, _Z, _P]),
+    "imf_tsdf_allocate_workspace_bytes": (_Z, [_L]),
+    "imf_tsdf_allocate": (_I, [_P, _I, _P, C.POINTER(TsdfParams), _I, _P, _L, _P, _L, _P, _P, _Z, _P]),
+    "imf_tsdf_integrate": (_I, [_P, _I, _P, C.POINTER(TsdfParams), _P, _P, _L, _P, _P]),
+    "imf_tsdf_extract_workspace_bytes": (_Z, [_L]),
+    "imf_tsdf_extract": (_I, [_P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _L, _P, _P, _Z, _P]),
     "imf_hash_capacity": (_L, [_L]),
     "imf_unique_workspace_bytes": (_Z, [_L]),
     "imf_voxelize": (_I, [_P, _I, _L, _D, _I, _P, _P, _P, _P, _L, _P, _P, _P]),

@@ -80,6 +80,72 @@ inline int paeth(int a, int b, int c) {
   return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
+// A PNG file's header fields, palette and concatenated IDAT stream: the chunks walked, nothing decoded yet.
+struct PngFile {
+  int W = 0, H = 0, depth = 0, ct = 0, interlace = 0;
+  bool transparency = false;
+  std::vector<unsigned char> idat, plte;
+};
+
+int png_chunks(const char *what, const char *path, PngFile &png) {
+  File fh(path, "rb");
+  IMF_REQUIRE(fh.f, "%s: cannot open %s", what, path);
+  const long size = fh.size();
+  IMF_REQUIRE(size > 33, "%s: %s is not a PNG file", what, path);
+  std::vector<unsigned char> buf((size_t)size);
+  IMF_REQUIRE(fread(buf.data(), 1, buf.size(), fh.f) == buf.size() && !memcmp(buf.data(), "\x89PNG\r\n\x1a\n", 8),
+              "%s: %s is not a PNG file", what, path);
+  size_t pos = 8;
+  while (pos + 12 <= buf.size()) {
+    const uint32_t len = be32(&buf[pos]);
+    const unsigned char *type = &buf[pos + 4], *data = &buf[pos + 8];
+    if ((unsigned long long)pos + 12 + len > buf.size()) break;
+    if (!memcmp(type, "IHDR", 4)) {
+      IMF_REQUIRE(len >= 13, "%s: short IHDR chunk in %s", what, path);
+      png.W = (int)be32(data); png.H = (int)be32(data + 4); png.depth = data[8]; png.ct = data[9]; png.interlace = data[12];
+    }
+    else if (!memcmp(type, "tRNS", 4)) png.transparency = true;
+    else if (!memcmp(type, "PLTE", 4)) png.plte.assign(data, data + len);
+    else if (!memcmp(type, "IDAT", 4)) png.idat.insert(png.idat.end(), data, data + len);
+    else if (!memcmp(type, "IEND", 4)) break;
+    pos += 12 + len;
+  }
+  return IMF_OK;
+}
+
+// raw = H rows of one filter byte + `row` bytes
+int png_inflate(const char *what, const char *path, const PngFile &png, size_t row, std::vector<unsigned char> &raw) {
+  // deflate expands at most ~1032x: a header that promises more pixels than the IDAT stream can hold is corrupt
+  IMF_REQUIRE((unsigned long long)(row + 1) * (unsigned long long)png.H <= 1040ull * (unsigned long long)png.idat.size() + 64,
+              "%s: %s declares %dx%d pixels but holds %zu bytes of image data", what, path, png.W, png.H, png.idat.size());
+  raw.resize((row + 1) * png.H);
+  uLongf raw_len = (uLongf)raw.size();
+  IMF_REQUIRE(uncompress(raw.data(), &raw_len, png.idat.data(), (uLong)png.idat.size()) == Z_OK && raw_len == raw.size(),
+              "%s: corrupt image data in %s", what, path);
+  return IMF_OK;
+}
+
+// one row's filter undone: src = the row's filter byte and bytes, prev = the row above (zeros for the first), cur = out
+int png_unfilter(const char *what, const char *path, const unsigned char *src, size_t row, int bpp,
+                 const std::vector<unsigned char> &prev, std::vector<unsigned char> &cur) {
+  const int ft = src[0];
+  ++src;
+  for (size_t i = 0; i < row; ++i) {
+    const int a = i >= (size_t)bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= (size_t)bpp ? prev[i - bpp] : 0;
+    int v = src[i];
+    switch (ft) {
+      case 0: break;
+      case 1: v += a; break;
+      case 2: v += b; break;
+      case 3: v += (a + b) >> 1; break;
+      case 4: v += paeth(a, b, c); break;
+      default: set_error("%s: bad filter type in %s", what, path); return IMF_EINVAL;
+    }
+    cur[i] = (unsigned char)v;
+  }
+  return IMF_OK;
+}
+
 // Helper threads of the block-parallel deflate: ONE pool per process, grown on demand and kept.  A std::thread per call was
 // measured to cap the box at ~300 files/s however the writers x threads were split (every thread start maps and unmaps an
 // 8 MiB stack: the same address-space lock as the per-block buffers before them).
@@ -284,35 +350,15 @@ int imf_png_info(const char *path, int *h, int *w, int *channels) {
  * else returns IMF_EUNSUPPORTED and the caller falls back to its generic decoder. */
 int imf_png_read_f32(const char *path, float *out, int64_t capacity_floats, int *h_out, int *w_out, int *c_out) {
   return guarded<int>("imf_png_read_f32", [&]() -> int {
+  const char *what = "imf_png_read_f32";
   IMF_REQUIRE(path && out && h_out && w_out && c_out, "imf_png_read_f32: null pointer");
-  File fh(path, "rb");
-  IMF_REQUIRE(fh.f, "imf_png_read_f32: cannot open %s", path);
-  const long size = fh.size();
-  IMF_REQUIRE(size > 33, "imf_png_read_f32: %s is not a PNG file", path);
-  std::vector<unsigned char> buf((size_t)size);
-  IMF_REQUIRE( fread(buf.data(), 1, buf.size(), fh.f) == buf.size() && !memcmp(buf.data(), "\x89PNG\r\n\x1a\n", 8),
-              "imf_png_read_f32: %s is not a PNG file", path);
-  int W = 0, H = 0, depth = 0, ct = 0, interlace = 0;
-  std::vector<unsigned char> idat, plte;
-  size_t pos = 8;
-  bool transparency = false;
-  while (pos + 12 <= buf.size()) {
-    const uint32_t len = be32(&buf[pos]);
-    const unsigned char *type = &buf[pos + 4], *data = &buf[pos + 8];
-    if ((unsigned long long)pos + 12 + len > buf.size()) break;
-    if (!memcmp(type, "IHDR", 4)) {
-      IMF_REQUIRE(len >= 13, "imf_png_read_f32: short IHDR chunk in %s", path);
-      W = (int)be32(data); H = (int)be32(data + 4); depth = data[8]; ct = data[9]; interlace = data[12];
-    }
-    else if (!memcmp(type, "tRNS", 4)) transparency = true;
-    else if (!memcmp(type, "PLTE", 4)) plte.assign(data, data + len);
-    else if (!memcmp(type, "IDAT", 4)) idat.insert(idat.end(), data, data + len);
-    else if (!memcmp(type, "IEND", 4)) break;
-    pos += 12 + len;
-  }
+  PngFile png;
+  int rc = png_chunks(what, path, png);
+  if (rc) return rc;
+  const int W = png.W, H = png.H, depth = png.depth, ct = png.ct;
   // tRNS: matplotlib returns RGBA for such files; 16-bit RGB(A): matplotlib / PIL go through an 8-bit path -- neither is
   // reproduced here, the caller's generic decoder takes them
-  if (interlace != 0 || (depth != 8 && depth != 16) || (ct == 3 && depth != 8) || transparency ||
+  if (png.interlace != 0 || (depth != 8 && depth != 16) || (ct == 3 && depth != 8) || png.transparency ||
       (depth == 16 && (ct == 2 || ct == 6))) {
     set_error("imf_png_read_f32: %s: interlaced / sub-byte / tRNS / 16-bit colour PNG not handled natively", path);
     return IMF_EUNSUPPORTED;
@@ -323,31 +369,14 @@ int imf_png_read_f32(const char *path, float *out, int64_t capacity_floats, int 
   IMF_REQUIRE((int64_t)H * W * C <= capacity_floats, "imf_png_read_f32: %dx%dx%d exceeds the capacity", H, W, C);
   const int bpp = samples * depth / 8;                         // bytes per pixel
   const size_t row = (size_t)W * bpp;
-  // deflate expands at most ~1032x: a header that promises more pixels than the IDAT stream can hold is corrupt
-  IMF_REQUIRE((unsigned long long)(row + 1) * (unsigned long long)H <= 1040ull * (unsigned long long)idat.size() + 64,
-              "imf_png_read_f32: %s declares %dx%d pixels but holds %zu bytes of image data", path, W, H, idat.size());
-  std::vector<unsigned char> raw((row + 1) * H);
-  uLongf raw_len = (uLongf)raw.size();
-  IMF_REQUIRE(uncompress(raw.data(), &raw_len, idat.data(), (uLong)idat.size()) == Z_OK && raw_len == raw.size(),
-              "imf_png_read_f32: corrupt image data in %s", path);
+  std::vector<unsigned char> raw;
+  rc = png_inflate(what, path, png, row, raw);
+  if (rc) return rc;
+  const std::vector<unsigned char> &plte = png.plte;
   std::vector<unsigned char> prev(row, 0), cur(row);
   for (int y = 0; y < H; ++y) {
-    const unsigned char *src = &raw[(row + 1) * y];
-    const int ft = src[0];
-    ++src;
-    for (size_t i = 0; i < row; ++i) {
-      const int a = i >= (size_t)bpp ? cur[i - bpp] : 0, b = prev[i], c = i >= (size_t)bpp ? prev[i - bpp] : 0;
-      int v = src[i];
-      switch (ft) {
-        case 0: break;
-        case 1: v += a; break;
-        case 2: v += b; break;
-        case 3: v += (a + b) >> 1; break;
-        case 4: v += paeth(a, b, c); break;
-        default: set_error("imf_png_read_f32: bad filter type in %s", path); return IMF_EINVAL;
-      }
-      cur[i] = (unsigned char)v;
-    }
+    rc = png_unfilter(what, path, &raw[(row + 1) * y], row, bpp, prev, cur);
+    if (rc) return rc;
     float *dst = out + (size_t)y * W * C;
     if (ct == 3) {
       for (int x = 0; x < W; ++x) {
@@ -362,6 +391,62 @@ int imf_png_read_f32(const char *path, float *out, int64_t capacity_floats, int 
     prev.swap(cur);
   }
   *h_out = H; *w_out = W; *c_out = C;
+  return IMF_OK;
+  });
+}
+
+/* A depth map as the sensor wrote it: 16-bit greyscale, non-interlaced (the 3DMatch / 7-Scenes `.depth.png`), samples
+ * big-endian in the file -> host-order uint16 [H,W].  Any other kind of PNG returns IMF_EUNSUPPORTED. */
+int imf_png_read_u16(const char *path, uint16_t *out, int64_t capacity_samples, int *h_out, int *w_out) {
+  return guarded<int>("imf_png_read_u16", [&]() -> int {
+  const char *what = "imf_png_read_u16";
+  IMF_REQUIRE(path && out && h_out && w_out, "imf_png_read_u16: null pointer");
+  PngFile png;
+  int rc = png_chunks(what, path, png);
+  if (rc) return rc;
+  const int W = png.W, H = png.H;
+  if (png.interlace != 0 || png.depth != 16 || png.ct != 0) {
+    set_error("imf_png_read_u16: %s is not a non-interlaced 16-bit greyscale PNG", path);
+    return IMF_EUNSUPPORTED;
+  }
+  IMF_REQUIRE(W > 0 && H > 0, "imf_png_read_u16: bad IHDR in %s", path);
+  IMF_REQUIRE((int64_t)H * W <= capacity_samples, "imf_png_read_u16: %dx%d exceeds the capacity", H, W);
+  const size_t row = (size_t)W * 2;
+  std::vector<unsigned char> raw;
+  rc = png_inflate(what, path, png, row, raw);
+  if (rc) return rc;
+  std::vector<unsigned char> prev(row, 0), cur(row);
+  for (int y = 0; y < H; ++y) {
+    rc = png_unfilter(what, path, &raw[(row + 1) * y], row, 2, prev, cur);
+    if (rc) return rc;
+    uint16_t *dst = out + (size_t)y * W;
+    for (int x = 0; x < W; ++x) dst[x] = (uint16_t)((cur[2 * x] << 8) | cur[2 * x + 1]);
+    prev.swap(cur);
+  }
+  *h_out = H; *w_out = W;
+  return IMF_OK;
+  });
+}
+
+/* Points as a binary little-endian PLY, `float x, y, z` per vertex.  The file appears under its name only when it is
+ * complete (temporary file + rename). */
+int imf_ply_write_points(const char *path, const double *xyz, int64_t n) {
+  return guarded<int>("imf_ply_write_points", [&]() -> int {
+  IMF_REQUIRE(path && (xyz || n == 0) && n >= 0 && n < (1ll << 31), "imf_ply_write_points: path=%p xyz=%p n=%lld",
+              (const void *)path, (const void *)xyz, (long long)n);
+  const std::string tmp = std::string(path) + ".tmp";
+  File fh(tmp.c_str(), "wb");
+  IMF_REQUIRE(fh.f, "imf_ply_write_points: cannot open %s (%s)", tmp.c_str(), strerror(errno));
+  fprintf(fh.f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
+                "property float z\nend_header\n", (long long)n);
+  std::vector<float> body((size_t)n * 3);
+  for (size_t i = 0; i < body.size(); ++i) body[i] = (float)xyz[i];
+  const bool wrote = fwrite(body.data(), sizeof(float), body.size(), fh.f) == body.size();
+  if (!(fh.close() && wrote) || rename(tmp.c_str(), path) != 0) {
+    remove(tmp.c_str());
+    set_error("imf_ply_write_points: cannot write %s (%s)", path, strerror(errno));
+    return IMF_EINVAL;
+  }
   return IMF_OK;
   });
 }

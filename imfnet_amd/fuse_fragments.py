@@ -1,0 +1,204 @@
+"""Fragments from raw RGB-D sequences: data/fuse_fragments_3DMatch.py with the same options and directory contract, the
+volume on the GPU (imfnet_amd/fuse.py, csrc/tsdf.hip).
+
+    python -m imfnet_amd.fuse_fragments --dataset_root <raw> --out_root <fragments>
+
+    <raw>/<scene>/camera-intrinsics.txt, <raw>/<scene>/<seq>/*.color.jpg + .depth.png + .pose.txt
+ -> <out>/<scene>/<seq>/cloud_bin_K.ply, cloud_bin_K.pose.npy, cloud_bin_K.frames.pkl
+
+Kept from upstream: sequences and colour files in alphanumeric order; fragments of --frames_per_frag frames; poses read
+as float32 and made relative to the fragment's first frame; a frame whose pose holds a NaN is skipped; a fragment whose
+first frame has no pose writes nothing; voxel length --tsdf_cubic_size / 512 and a 0.04 m truncation.
+The project's own: --voxel_length and --lattice_offset (0.5 = upstream's voxel centres; 0 with --voxel_length 0.006
+gives the lattice of the published 3DMatch fragments); --write_image copies the first integrated frame's
+colour file to cloud_bin_K_0.jpg, the name generate_desc and the trainer look for (upstream writes no image; which frame
+its data set used is not recorded).  The PLY holds float x, y, z only: no colours, no normals.  --threads sizes the
+decode pool (upstream: joblib workers); the next fragment is decoded while the GPU works on the current one.
+"""
+import argparse
+import concurrent.futures as cf
+import ctypes as C
+import math
+import os
+import pickle
+import shutil
+import sys
+
+import numpy as np
+import torch  # noqa: F401  (before the native library is loaded: both must share one HIP runtime)
+
+from . import _lib
+from .files import ensure_dir, sorted_alphanum
+
+SDF_TRUNC = 0.04
+
+
+def cpu_quota():
+    """CPUs this process may use: its affinity mask, a cgroup quota and OMP_NUM_THREADS, whichever is least."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) / int(period))))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, max(1, int(os.environ["OMP_NUM_THREADS"])))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
+def list_folders(path, alphanum=True):
+    names = [f for f in os.listdir(path) if os.path.isdir(os.path.join(path, f))]
+    return sorted_alphanum(names) if alphanum else names
+
+
+def list_color_files(seq_folder):
+    return sorted_alphanum([f for f in os.listdir(seq_folder) if f.endswith(".color.jpg")])
+
+
+def read_extrinsic(path):
+    """float32 4x4, or None when the file holds a NaN (a lost track) -- upstream's read_extrinsic."""
+    m = np.loadtxt(path, dtype=np.float32)
+    return None if np.isnan(m).any() else m
+
+
+def read_depth_png(path, height, width):
+    """uint16 [height, width] (imf_png_read_u16; PIL for the kinds of PNG the native reader leaves out)."""
+    L = _lib.lib()
+    out = np.empty((height, width), np.uint16)
+    h, w = C.c_int(), C.c_int()
+    rc = L.imf_png_read_u16(os.fsencode(path), out.ctypes.data_as(C.c_void_p), out.size, C.byref(h), C.byref(w))
+    if rc == -3:                                             # IMF_EUNSUPPORTED
+        from PIL import Image
+        with Image.open(path) as im:
+            a = np.asarray(im)
+        if a.shape != (height, width):
+            raise ValueError(f"{path}: {a.shape}, expected ({height}, {width})")
+        return a.astype(np.uint16)
+    _lib.check(rc, f"imf_png_read_u16({path})")
+    if (h.value, w.value) != (height, width):
+        raise ValueError(f"{path}: {h.value} x {w.value}, expected {height} x {width} (--height / --width)")
+    return out
+
+
+def fragment_ranges(n_frames, frames_per_frag):
+    """[(frag_id, first frame, one past the last)]."""
+    n_frags = int(math.ceil(float(n_frames) / frames_per_frag))
+    return [(k, k * frames_per_frag, min((k + 1) * frames_per_frag, n_frames)) for k in range(n_frags)]
+
+
+def select_frames(color_paths, sid, eid, read_pose=read_extrinsic):
+    """Upstream's loop over a fragment's frames without the volume: (base pose or None, [(frame stem, relative pose)]).
+    A NaN pose skips the frame; if that was the first frame there is no base pose and the fragment ends at the next frame
+    that has one, empty."""
+    base = base_inv = None
+    frames = []
+    for fid in range(sid, eid):
+        stem = color_paths[fid][:-10]
+        pose = read_pose(stem + ".pose.txt")
+        if pose is None:
+            continue
+        if fid == sid:
+            base, base_inv = pose, np.linalg.inv(pose)
+        if base_inv is None:
+            break
+        frames.append((stem, np.matmul(base_inv, pose)))
+    return base, frames
+
+
+def load_fragment(cfg, color_paths, sid, eid, pool):
+    """Poses and decoded depth of one fragment, or None when it writes nothing."""
+    base, frames = select_frames(color_paths, sid, eid)
+    if base is None:
+        return None
+    depth = list(pool.map(lambda fr: read_depth_png(fr[0] + ".depth.png", cfg.height, cfg.width), frames))
+    depth = np.stack(depth) if depth else np.zeros((0, cfg.height, cfg.width), np.uint16)
+    poses = np.stack([p for _, p in frames]).astype(np.float64) if frames else np.zeros((0, 4, 4))
+    return dict(base=base, stems=[s for s, _ in frames], depth=depth, poses=poses)
+
+
+def write_ply(path, xyz):
+    xyz = np.ascontiguousarray(xyz, np.float64)
+    rc = _lib.lib().imf_ply_write_points(os.fsencode(path), xyz.ctypes.data_as(C.c_void_p), len(xyz))
+    _lib.check(rc, f"imf_ply_write_points({path})")
+
+
+def write_fragment(cfg, out_folder, frag_id, frag, xyz):
+    write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz)
+    np.save(os.path.join(out_folder, f"cloud_bin_{frag_id}.pose.npy"), frag["base"])
+    with open(os.path.join(out_folder, f"cloud_bin_{frag_id}.frames.pkl"), "wb") as fh:
+        pickle.dump({"frames": frag["stems"]}, fh, protocol=pickle.HIGHEST_PROTOCOL)
+    if cfg.write_image and frag["stems"]:
+        shutil.copyfile(frag["stems"][0] + ".color.jpg", os.path.join(out_folder, f"cloud_bin_{frag_id}_0.jpg"))
+
+
+def gpu_fuse(cfg, intrinsic, frag):
+    from .fuse import fuse_fragment
+    return fuse_fragment(frag["depth"], frag["poses"], intrinsic, voxel_length=cfg.voxel_length, sdf_trunc=SDF_TRUNC,
+                         depth_scale=cfg.depth_scale, depth_trunc=cfg.depth_trunc, lattice_offset=cfg.lattice_offset,
+                         device=cfg.device)
+
+
+def run(cfg, fuse=gpu_fuse, log=print):
+    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` does the volume work.  Returns the fragments written."""
+    if cfg.voxel_length is None:
+        cfg.voxel_length = cfg.tsdf_cubic_size / 512.0
+    ensure_dir(cfg.out_root)
+    jobs = []                                                # (scene, seq, intrinsic, color paths, frag id, sid, eid)
+    for scene in list_folders(cfg.dataset_root, alphanum=False):
+        intrinsic = np.loadtxt(os.path.join(cfg.dataset_root, scene, "camera-intrinsics.txt"), dtype=np.float32)
+        for seq in list_folders(os.path.join(cfg.dataset_root, scene)):
+            folder = os.path.join(cfg.dataset_root, scene, seq)
+            colors = [os.path.join(folder, f) for f in list_color_files(folder)]
+            ensure_dir(os.path.join(cfg.out_root, scene, seq))
+            for k, sid, eid in fragment_ranges(len(colors), cfg.frames_per_frag):
+                jobs.append((scene, seq, intrinsic.astype(np.float64), colors, k, sid, eid))
+    written = 0
+    threads = max(1, min(cfg.threads or cpu_quota(), cpu_quota()))
+    with cf.ThreadPoolExecutor(threads) as pool, cf.ThreadPoolExecutor(1) as ahead:
+        submit = lambda j: ahead.submit(load_fragment, cfg, j[3], j[5], j[6], pool)
+        nxt = submit(jobs[0]) if jobs else None
+        for i, (scene, seq, intrinsic, colors, k, sid, eid) in enumerate(jobs):
+            frag = nxt.result()
+            nxt = submit(jobs[i + 1]) if i + 1 < len(jobs) else None      # decoded while the GPU fuses this one
+            if frag is None:
+                log(f"    {scene}/{seq} fragment {k}: no pose for its first frame, nothing written")
+                continue
+            xyz = fuse(cfg, intrinsic, frag)
+            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz)
+            written += 1
+            log(f"    {scene}/{seq}/cloud_bin_{k}: {len(frag['stems'])} frames, {len(xyz)} points")
+    return written
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset_root", required=True)
+    ap.add_argument("--out_root", required=True)
+    ap.add_argument("--depth_scale", type=float, default=1000.0)
+    ap.add_argument("--depth_trunc", type=float, default=6.0)
+    ap.add_argument("--frames_per_frag", type=int, default=50)
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--threads", type=int, default=0, help="decode threads (0 = the CPU quota)")
+    ap.add_argument("--tsdf_cubic_size", type=float, default=3.0)
+    ap.add_argument("--voxel_length", type=float, default=None, help="metres (default: tsdf_cubic_size / 512)")
+    ap.add_argument("--lattice_offset", type=float, default=0.5,
+                    help="0.5 = voxel centres (upstream); 0 = voxel corners (the published fragments, with --voxel_length 0.006)")
+    ap.add_argument("--write_image", action="store_true", help="copy the first integrated frame's colour file to cloud_bin_K_0.jpg")
+    ap.add_argument("--device", default="cuda")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    cfg = parse_args(argv)
+    n = run(cfg)
+    print(f"{n} fragments written to {cfg.out_root}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

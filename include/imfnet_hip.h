@@ -875,6 +875,46 @@ size_t imf_robust_transform_workspace_bytes(int64_t n);
 int imf_robust_transform(const double *pts0, const double *pts1, const double *weight, int64_t n, double *out_T,
                          int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Fragment fusion: depth frames -> sparse TSDF volume -> surface points (imfnet_amd/fuse.py) -------------------------
+ * Replace Open3D 0.12 ScalableTSDFVolume(voxel_length, sdf_trunc).integrate(...) per frame and extract_point_cloud() as
+ * data/fuse_fragments_3DMatch.py:47-96 builds a fragment (the loop restated in csrc/tsdf.hip; no colour, no normals).
+ * The volume is a set of units of 16^3 voxels: `table` (imf_slot[table_capacity], a power of two >= 2 unit_capacity:
+ * imf_hash_capacity(unit_capacity)) maps a unit's integer coordinate to its row, `units` int32 [unit_capacity,3] = (x, y, z)
+ * lists the rows in ascending (z, y, x), `voxels` float32 [rows, 4096, 2] = (tsdf, weight) of voxel (z * 16 + y) * 16 + x,
+ * zeroed by the caller.  A voxel's sample position is (16 unit + local + lattice_offset) * voxel_length per axis:
+ * lattice_offset 0.5 = Open3D's voxel centres, 0 = the lattice the published 3DMatch fragments lie on.  All buffers are
+ * device memory of the caller; depth is uint16 [n_frames, height, width]; the matrices are device fp64 [n_frames, 12],
+ * row-major 3x4.  No host synchronisation, integer atomics only, a fixed frame order: bit-identical from run to run.
+ * workspace: 256-byte aligned.  The *_workspace_bytes queries answer 0 for a size the call refuses. */
+typedef struct imf_tsdf_params {
+  double fx, fy, cx, cy;       /* pinhole intrinsics in pixels                                              */
+  double voxel_length;         /* m; upstream: tsdf_cubic_size / 512                                        */
+  double sdf_trunc;            /* m; upstream: 0.04                                                         */
+  double depth_scale;          /* raw depth units per metre (1000); the quotient is taken in float32        */
+  double depth_trunc;          /* m; a depth beyond it is no measurement                                    */
+  double lattice_offset;       /* in [0, 1): 0.5 or 0                                                       */
+  int32_t height, width;
+} imf_tsdf_params;
+/* Opens the units around every stride-4 depth sample of all frames (cam2world: camera -> volume) and rebuilds the sorted
+ * unit list.  reset != 0 empties the table first; reset == 0 adds to it (rows change: only before the first integrate).
+ * n_units: device int32[2] = {units in the table, flags: 1 = a sample beyond the coordinate range or a NaN pose was left
+ * out, 2 = more than unit_capacity units: list and rows are incomplete, call again with more room}. */
+size_t imf_tsdf_allocate_workspace_bytes(int64_t unit_capacity);
+int imf_tsdf_allocate(const uint16_t *depth, int n_frames, const double *cam2world, const imf_tsdf_params *params,
+                      int reset, imf_slot *table, int64_t table_capacity, int32_t *units, int64_t unit_capacity,
+                      int32_t *n_units, void *workspace, size_t workspace_bytes, void *stream);
+/* The running average of every voxel of the first min(n_units[0], max_units) units over the frames in frame order
+ * (world2cam: volume -> camera).  One workgroup per unit; max_units workgroups are launched. */
+int imf_tsdf_integrate(const uint16_t *depth, int n_frames, const double *world2cam, const imf_tsdf_params *params,
+                       const int32_t *units, const int32_t *n_units, int64_t max_units, float *voxels, void *stream);
+/* One point per sign change between a voxel and its +x / +y / +z neighbour, fp64 [n,3] in the order (unit, voxel, axis).
+ * out_n: device int64[1], always written; when it exceeds capacity nothing is written to out (capacity 0: count only,
+ * out may be NULL). */
+size_t imf_tsdf_extract_workspace_bytes(int64_t max_units);
+int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
+                     const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out,
+                     int64_t capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Training backward of the sparse convolution (last item) ---------------------------------------
  * Replaces: the backward of ME.MinkowskiConvolution / ConvolutionTranspose under loss.backward(), lib/trainer.py:495-569.
  * The INPUT gradient is imf_spconv_fwd itself over the opposite kernel map with transposed weights
@@ -900,6 +940,13 @@ int imf_png_info(const char *path, int *h, int *w, int *channels);
 /* matplotlib.image.imread of a .png: float32 [H,W,C] in [0,1] (8-bit / 255, 16-bit / 65535, palette -> RGB).
  * IMF_EUNSUPPORTED for interlaced or sub-byte files (callers fall back to a generic decoder). */
 int imf_png_read_f32(const char *path, float *out, int64_t capacity_floats, int *h, int *w, int *channels);
+/* o3d.io.read_image of a depth map (data/fuse_fragments_3DMatch.py:41): 16-bit greyscale PNG, big-endian samples ->
+ * host-order uint16 [H,W].  IMF_EUNSUPPORTED for every other kind of PNG. */
+int imf_png_read_u16(const char *path, uint16_t *out, int64_t capacity_samples, int *h, int *w);
+/* A fragment's points as a binary little-endian PLY with `float x, y, z` per vertex (fp64 [n,3] in, narrowed to
+ * float32: the 3DMatch fragments' layout, which imf_ply_read_points reads).  Written through a temporary file and a
+ * rename. */
+int imf_ply_write_points(const char *path, const double *xyz, int64_t n);
 
 /* matplotlib.image.imread of a .jpg (scripts/generate_desc.py:88-92: PIL = libjpeg's defaults, integer "islow" inverse DCT
  * and fancy chroma upsampling): uint8 [H, W, 3].  Baseline / extended sequential Huffman files with three YCbCr components in

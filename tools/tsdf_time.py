@@ -1,0 +1,106 @@
+"""Time of the fragment fusion (imfnet_amd/fuse.py, csrc/tsdf.hip) on one synthetic fragment of 50 frames at 640 x 480
+(tests/tsdf_scene.py), next to the NumPy restatement (tests/tsdf_restate.py) on the same input.
+
+  allocate / integrate / extract   each call between device synchronisations, inputs resident (medians)
+  fragment                          fuse_fragment host to host: upload of the depth frames, the three calls, the download
+  restatement                       the NumPy restatement, its units split over at most 16 threads (one run)
+  integrate_bytes_per_s             units x 4096 voxels x 8 B read and written once, over the integrate time
+
+Usage: python tools/tsdf_time.py [--iters 5] [--warmup 2] [--frames 50] [--no-restatement] [--out FILE.json]
+Prints one JSON line (milliseconds, medians)."""
+import argparse
+import concurrent.futures as cf
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def median_ms(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(iters):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(out))
+
+
+def restate_threaded(R, seq, threads):
+    p = R.params()
+    c2w = seq["poses"]
+    units = R.allocate(seq["depth"], c2w, seq["K"], p)
+    w2c = np.linalg.inv(c2w)
+    chunks = np.array_split(np.arange(len(units)), max(1, min(len(units) // 64, threads * 4)))
+    with cf.ThreadPoolExecutor(threads) as pool:
+        parts = list(pool.map(lambda ix: R.integrate(units[ix], seq["depth"], w2c, seq["K"], p), chunks))
+    tsdf, w = np.concatenate([a for a, _ in parts]), np.concatenate([b for _, b in parts])
+    return R.extract(units, tsdf, w, p)[0], units
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=50)
+    ap.add_argument("--no-restatement", action="store_true")
+    ap.add_argument("--out", type=str, default=None)
+    a = ap.parse_args()
+    import tsdf_restate as R
+    import tsdf_scene as S
+    from imfnet_amd.fuse import TSDFVolume, fuse_fragment
+    assert torch.cuda.is_available(), "tsdf_time needs a GPU"
+    seq = S.make_sequence(640, 480, n_frames=a.frames, arc=1.2)
+    H, W = seq["depth"].shape[1:]
+    res = {"device": torch.cuda.get_device_name(0), "frames": a.frames, "height": H, "width": W, "iters": a.iters,
+           "warmup": a.warmup, "voxel_length": 3.0 / 512, "lattice_offset": 0.5}
+    dev = torch.device("cuda:0")
+    d = torch.from_numpy(seq["depth"].view(np.int16)).to(dev)
+    state = {}
+
+    def allocate():
+        state["vol"] = TSDFVolume(seq["K"], H, W, unit_capacity=1 << 16)
+        state["vol"].allocate(d, seq["poses"])
+
+    def integrate():
+        state["vol"]._voxels = None                           # a fresh volume each time: the same work every iteration
+        state["vol"].integrate(d, seq["poses"])
+
+    res["allocate_ms"] = median_ms(allocate, a.iters, a.warmup)
+    res["integrate_ms"] = median_ms(integrate, a.iters, a.warmup)
+    res["extract_ms"] = median_ms(lambda: state["vol"].extract(), a.iters, a.warmup)
+    pts = state["vol"].extract()
+    res["units"], res["points"] = state["vol"].n_units, int(len(pts))
+    res["integrate_state_bytes"] = res["units"] * 4096 * 8 * 2
+    res["integrate_bytes_per_s"] = res["integrate_state_bytes"] / (res["integrate_ms"] * 1e-3)
+    res["voxel_frame_updates_per_s"] = res["units"] * 4096 * a.frames / (res["integrate_ms"] * 1e-3)
+    res["fragment_ms"] = median_ms(lambda: fuse_fragment(seq["depth"], seq["poses"], seq["K"]), a.iters, a.warmup)
+    if not a.no_restatement:
+        threads = min(16, len(os.sched_getaffinity(0)))
+        t = time.perf_counter()
+        ref, units = restate_threaded(R, seq, threads)
+        res["restatement_ms"], res["restatement_threads"] = (time.perf_counter() - t) * 1e3, threads
+        res["restatement_units_equal"] = bool(units.shape == state["vol"].units.shape and (units == state["vol"].units).all())
+        res["restatement_points"] = int(len(ref))
+        if ref.shape == pts.shape:
+            res["max_abs_diff_vs_restatement"] = float(np.abs(ref - pts).max())
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
