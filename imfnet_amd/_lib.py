@@ -147,6 +147,12 @@ class TsdfParams(C.Structure):
                 ("depth_trunc", C.c_double), ("lattice_offset", C.c_double), ("height", C.c_int32), ("width", C.c_int32)]
 
 
+class OverlapIndex(C.Structure):
+    """struct imf_overlap_index."""
+    _fields_ = [("table", C.c_void_p), ("capacity", C.c_int64), ("xyz", C.c_void_p), ("idx", C.c_void_p),
+                ("cells", C.c_void_p), ("chunks", C.c_void_p), ("meta", C.c_void_p), ("n", C.c_int64), ("cell", C.c_double)]
+
+
 class Job(C.Structure):
     """struct imf_job (one forward of the streaming pipeline)."""
     _fields_ = [("net", C.POINTER(ResunetDesc)), ("img", C.POINTER(ImageDesc)), ("caps", C.POINTER(FragmentCaps)),
@@ -233,6 +239,13 @@ SIGNATURES = {
     "imf_tsdf_integrate": (_I, [_P, _I, _P, C.POINTER(TsdfParams), _P, _P, _L, _P, _P]),
     "imf_tsdf_extract_workspace_bytes": (_Z, [_L]),
     "imf_tsdf_extract": (_I, [_P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _L, _P, _P, _Z, _P]),
+    "imf_overlap_index_bytes": (_Z, [_L]),
+    "imf_overlap_index_workspace_bytes": (_Z, [_L]),
+    "imf_overlap_index_build": (_I, [_P, _L, _D, _P, _Z, C.POINTER(OverlapIndex), _P, _Z, _P]),
+    "imf_overlap_bound": (_I, [_P, _P, _I, _L, _P, _P]),
+    "imf_overlap_pair": (_I, [C.POINTER(OverlapIndex), C.POINTER(OverlapIndex), C.c_float, _L, _P, _P]),
+    "imf_overlap_emit_workspace_bytes": (_Z, [_L]),
+    "imf_overlap_emit": (_I, [_P, _L, _P, _P, _P, _Z, _P]),
     "imf_hash_capacity": (_L, [_L]),
     "imf_unique_workspace_bytes": (_Z, [_L]),
     "imf_voxelize": (_I, [_P, _I, _L, _D, _I, _P, _P, _P, _P, _L, _P, _P, _P]),

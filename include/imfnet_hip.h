@@ -915,6 +915,46 @@ int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n
                      const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out,
                      int64_t capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Fragment overlap: the 3DMatch training-pair builder (imfnet_amd/overlap.py, imfnet_amd.compute_overlap) ------------
+ * Replace the pyflann nearest-neighbour queries of data/compute_overlap.py:93-141 (the loop restated in csrc/overlap.hip):
+ * for a pair (p, q) every point of q gets its EXACT nearest point of p (float32 d2 = (dx dx + dy dy) + dz dz without
+ * fused multiply-adds, equal distances to the lowest p index), kept when sqrtf(d2) <= thresh; the rows (i, j) ascend in j.
+ * A sequence-level engine: an index per fragment, built once and resident; a bound for all candidate pairs in one launch;
+ * the exact pass and the emit per surviving pair.  All buffers are device memory of the caller unless marked HOST; no
+ * host synchronisation inside a call, integer atomics only, no atomic decides an output position: bit-identical from run
+ * to run.  workspace / storage: 256-byte aligned.  The *_bytes queries answer 0 for a size the call refuses. */
+typedef struct imf_overlap_index {
+  imf_slot *table;        /* [capacity] key = cell, val = first sorted row, pad = points of the cell             */
+  int64_t capacity;       /* imf_hash_capacity(n)                                                                */
+  float *xyz;             /* [n,3] the points sorted by cell                                                     */
+  int32_t *idx;           /* [n] original index of every sorted row                                              */
+  int32_t *cells;         /* [n] slots of the occupied cells, ascending; meta[0] are valid                       */
+  int32_t *chunks;        /* [n,2] (slot, first point within the cell) of every run of <= 256 points; meta[1]    */
+  int32_t *meta;          /* [4] occupied cells, chunks, flags (1 = a NaN / out-of-range point left out), points */
+  int64_t n;
+  double cell;            /* cell edge, m                                                                        */
+} imf_overlap_index;
+/* Builds the index of points float32 [n,3] into `storage` (imf_overlap_index_bytes(n)) and fills the HOST struct *index
+ * with pointers into it.  cell: the edge; imf_overlap_pair needs it above thresh (1 + 2^-20), see csrc/overlap.hip. */
+size_t imf_overlap_index_bytes(int64_t n);
+size_t imf_overlap_index_workspace_bytes(int64_t n);
+int imf_overlap_index_build(const float *points, int64_t n, double cell, void *storage, size_t storage_bytes,
+                            imf_overlap_index *index, void *workspace, size_t workspace_bytes, void *stream);
+/* The prefilter.  indices: DEVICE array of index structs; pairs: device int32 [n_pairs,2] = (p, q) positions in it;
+ * bound: device int64 [n_pairs] = the points of q whose cell has an occupied cell of p among its 27 neighbours, an upper
+ * bound of the exact pass's row count.  max_cells: at least the largest meta[0] of the q side.  n_pairs <= 65535. */
+int imf_overlap_bound(const imf_overlap_index *indices, const int32_t *pairs, int n_pairs, int64_t max_cells,
+                      int64_t *bound, void *stream);
+/* The exact pass.  p, q: HOST structs.  nn_idx: device int32 [q->n], the nearest p index of every point of q, -1 where
+ * none is within thresh.  max_chunks: at least q's meta[1] (workgroups launched). */
+int imf_overlap_pair(const imf_overlap_index *p, const imf_overlap_index *q, float thresh, int64_t max_chunks,
+                     int32_t *nn_idx, void *stream);
+/* Order-preserving compaction: pairs int64 [n_q,2] receives the rows (nn_idx[j], j) with nn_idx[j] >= 0 in ascending j,
+ * out_n: device int64[1] their number. */
+size_t imf_overlap_emit_workspace_bytes(int64_t n_q);
+int imf_overlap_emit(const int32_t *nn_idx, int64_t n_q, int64_t *pairs, int64_t *out_n, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* ---- Training backward of the sparse convolution (last item) ---------------------------------------
  * Replaces: the backward of ME.MinkowskiConvolution / ConvolutionTranspose under loss.backward(), lib/trainer.py:495-569.
  * The INPUT gradient is imf_spconv_fwd itself over the opposite kernel map with transposed weights
