@@ -11,6 +11,13 @@ MinkowskiEngine's autograd, lib/trainer.py:495-569).
               1x1x1         grad @ W^T
   d kernel  imf_spconv_wgrad (csrc/backward.hip): per offset the sum of in[i]^T grad[o] over the map's pairs.
 Everything stays on the GPU; the maps come from the coordinate manager's cache (built once per fragment).
+
+Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
+two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
+range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
+everything (below 6e-8), an activation at or above 65504 would become inf, and this path has neither the range flag nor
+the fp32 recompute that guard inference.  Packing costs the same, and the weight gradient is plain fp32 anyway.
+tests/test_gpu_backward_exact.py pins it with gradients scaled by 2^-30 and by 2^20.
 """
 import ctypes as C
 
@@ -33,6 +40,13 @@ def _opposite_rulebook(cm, ts_in, ksize, stride, transposed):
             return cm.conv_rulebook(ts_in, ksize, 1)                  # symmetric: same map, flipped offsets
         return cm.transpose_rulebook(ts_in * stride, ksize, stride)  # outputs live at ts_in * stride: coarse -> fine
     return cm.conv_rulebook(ts_in // stride, ksize, stride)          # transposed conv: fine (outputs) -> coarse (inputs)
+
+
+def training_variant(kvol):
+    """The arithmetic of a differentiable convolution: the process-wide one, except that the split-f16 fast mode (6) is
+    replaced by bf16x3 (3) -- see the module docstring."""
+    variant = ops.conv_variant_for(kvol)
+    return 3 if variant == 6 else variant
 
 
 def spconv_wgrad(feat, grad_out, rb, kvol):
@@ -58,7 +72,7 @@ class SparseConvFunction(torch.autograd.Function):
         if module.in_channels <= 4:
             out = ops.spconv_small_cin(feat_c, k3.detach(), rb)
         else:
-            variant = ops.conv_variant_for(module.kernel_volume)
+            variant = training_variant(module.kernel_volume)
             out = ops.spconv(feat_c, ops.pack_weights(k3.detach(), variant=variant), module.out_channels, rb,
                              variant=variant)
         ctx.save_for_backward(feat_c, kernel)
@@ -85,7 +99,7 @@ class SparseConvFunction(torch.autograd.Function):
                 wt = k3.transpose(1, 2)
                 if not m._transposed and m.stride == 1:
                     wt = wt.flip(0)
-                variant = ops.conv_variant_for(K)
+                variant = training_variant(K)
                 grad_feat = ops.spconv(g, ops.pack_weights(wt.contiguous(), variant=variant), m.in_channels, rbt,
                                        variant=variant)
         if ctx.needs_input_grad[1]:

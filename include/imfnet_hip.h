@@ -962,7 +962,12 @@ int imf_overlap_emit(const int32_t *nn_idx, int64_t n_q, int64_t *pairs, int64_t
  * strided map for a transposed one).  The WEIGHT gradient is this entry point:
  *     dw[k][ci][co] = sum over the pairs (i, o) of offset k of  in[i][ci] * grad_out[o][co]
  * over the same rulebook the forward used (tile_rows / nbr as in imf_conv_args; nbr NULL = identity when kvol == 1).
- * Any cin, cout >= 1.  Deterministic (chunk partials summed in order).  workspace: imf_spconv_wgrad_workspace_bytes. */
+ * Any cin, cout >= 1 (tests/test_gpu_backward_exact.py::test_wgrad_is_exact_on_integer_data: channel counts off the
+ * 32-wide block, slot counts on and around the 4096-slot chunk, padding, permuted slots, empty offsets).  Deterministic:
+ * chunk partials summed in order, no float atomics, two calls give the same bits
+ * (::test_wgrad_on_float_data_is_reproducible_and_within_the_summation_bound).  fp32 on the vector pipe whatever the
+ * convolutions' arithmetic.  Bad arguments return IMF_EINVAL before any launch.
+ * workspace: imf_spconv_wgrad_workspace_bytes. */
 size_t imf_spconv_wgrad_workspace_bytes(int64_t n_slots, int kvol, int cin, int cout);
 int imf_spconv_wgrad(const float *in, int cin, const float *grad_out, int cout, const int32_t *tile_rows,
                      const int32_t *nbr, int64_t n_slots, int64_t n_out, int kvol, float *dw /* [kvol][cin][cout] */,

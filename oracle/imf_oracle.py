@@ -248,19 +248,25 @@ def instance_norm(x, item, weight, bias, eps=1e-8):
     return torch.from_numpy(out).float()
 
 
-def block_norm(x, sd, prefix, item):
+def batchnorm_train(x, sd, prefix, eps=1e-5):
+    """ME.MinkowskiBatchNorm in training mode: the statistics of the batch's own rows (biased variance), no running
+    statistics read or written."""
+    return F.batch_norm(x, None, None, sd[prefix + ".bn.weight"], sd[prefix + ".bn.bias"], True, 0.0, eps)
+
+
+def block_norm(x, sd, prefix, item, bn_training=False):
     """The block's norm layer by what the state dict holds: BatchNorm ('<prefix>.bn.*') or InstanceNorm ('<prefix>.weight')."""
     if prefix + ".bn.weight" in sd:
-        return batchnorm_eval(x, sd, prefix)
+        return batchnorm_train(x, sd, prefix) if bn_training else batchnorm_eval(x, sd, prefix)
     return instance_norm(x, item, sd[prefix + ".weight"], sd[prefix + ".bias"])
 
 
-def basic_block(x, sd, prefix, nbr, item=None):
+def basic_block(x, sd, prefix, nbr, item=None, bn_training=False):
     """model/residual_block.py:37-53 (BasicBlockBN / BasicBlockIN; `item`: the rows' batch indices, for IN)."""
     out = spconv(x, sd[prefix + ".conv1.kernel"], nbr)
-    out = F.relu(block_norm(out, sd, prefix + ".norm1", item))
+    out = F.relu(block_norm(out, sd, prefix + ".norm1", item, bn_training))
     out = spconv(out, sd[prefix + ".conv2.kernel"], nbr)
-    out = block_norm(out, sd, prefix + ".norm2", item)
+    out = block_norm(out, sd, prefix + ".norm2", item, bn_training)
     return F.relu(out + x)
 
 
@@ -268,9 +274,11 @@ def basic_block(x, sd, prefix, nbr, item=None):
 # dense parts
 # --------------------------------------------------------------------------
 
-def image_encoder(image, sd, prefix="img_encoder.backbone."):
-    """model/resnet.py:195-216 -- ResNet-34 truncated after layer2, BN in eval mode."""
+def image_encoder(image, sd, prefix="img_encoder.backbone.", bn_training=False):
+    """model/resnet.py:195-216 -- ResNet-34 truncated after layer2, BN in eval mode (bn_training: batch statistics)."""
     def bn(x, p):
+        if bn_training:
+            return F.batch_norm(x, None, None, sd[p + ".weight"], sd[p + ".bias"], True, 0.0, 1e-5)
         return F.batch_norm(x, sd[p + ".running_mean"], sd[p + ".running_var"],
                             sd[p + ".weight"], sd[p + ".bias"], False, 0.0, 1e-5)
 
@@ -282,7 +290,7 @@ def image_encoder(image, sd, prefix="img_encoder.backbone."):
             idt = bn(F.conv2d(x, sd[p + ".downsample.0.weight"], stride=stride), p + ".downsample.1")
         return F.relu(out + idt)
 
-    x = torch.as_tensor(image, dtype=torch.float32)
+    x = torch.as_tensor(image, dtype=sd[prefix + "conv1.weight"].dtype)     # float32; float64 for the yardstick runs
     x = F.relu(bn(F.conv2d(x, sd[prefix + "conv1.weight"], stride=2, padding=3), prefix + "bn1"))
     x = F.max_pool2d(x, 3, 2, 1)
     for i in range(3):
@@ -319,33 +327,40 @@ def attention_fusion(tokens, x, sd, prefix="attention_fusion.cross_attend_blocks
 # --------------------------------------------------------------------------
 
 def resunet_forward(sd, coords, image, feats=None, normalize_feature=True,
-                    conv1_kernel_size=5, geometry=None, taps=None):
+                    conv1_kernel_size=5, geometry=None, taps=None, bn_training=False):
     """ResUNetBN2C.forward(x, image).  coords int32 [M,4] unique rows grouped by batch,
     image f32 [B,3,H,W], feats f32 [M,Cin] (default ones, util/misc.py:76-79).
-    Returns F f32 [M,32].  `taps` (dict) collects intermediate tensors."""
+    Returns F f32 [M,32].  `taps` (dict) collects intermediate tensors.  bn_training: every BatchNorm (the sparse norms
+    and the image encoder's) uses the statistics of the batch, as model.train() does; off, nothing changes."""
     sd = {k: torch.as_tensor(v) for k, v in sd.items()}
     g = geometry or Geometry(coords, conv1_kernel_size)
     M = len(g.levels[0])
     x = torch.ones(M, 1) if feats is None else torch.as_tensor(feats, dtype=torch.float32)
     tap = (lambda n, t: taps.__setitem__(n, t.clone())) if taps is not None else (lambda n, t: None)
 
-    img = image_encoder(image, sd)                                        # :166
+    def norm(t, prefix):
+        return batchnorm_train(t, sd, prefix) if bn_training else batchnorm_eval(t, sd, prefix)
+
+    def block(t, prefix, nbr, item):
+        return basic_block(t, sd, prefix, nbr, item, bn_training)
+
+    img = image_encoder(image, sd, bn_training=bn_training)               # :166
     tap("image_feat", img)
 
-    out = batchnorm_eval(spconv(x, sd["conv1.kernel"], g.k_first), sd, "norm1")     # :168-169
-    out_s1 = basic_block(out, sd, "block1", g.k3[0], g.levels[0][:, 0])
+    out = norm(spconv(x, sd["conv1.kernel"], g.k_first), "norm1")     # :168-169
+    out_s1 = block(out, "block1", g.k3[0], g.levels[0][:, 0])
     out = F.relu(out_s1)
     tap("out_s1", out_s1)
-    out = batchnorm_eval(spconv(out, sd["conv2.kernel"], g.down[0]), sd, "norm2")   # :173-174
-    out_s2 = basic_block(out, sd, "block2", g.k3[1], g.levels[1][:, 0])
+    out = norm(spconv(out, sd["conv2.kernel"], g.down[0]), "norm2")   # :173-174
+    out_s2 = block(out, "block2", g.k3[1], g.levels[1][:, 0])
     out = F.relu(out_s2)
     tap("out_s2", out_s2)
-    out = batchnorm_eval(spconv(out, sd["conv3.kernel"], g.down[1]), sd, "norm3")   # :178-179
-    out_s4 = basic_block(out, sd, "block3", g.k3[2], g.levels[2][:, 0])
+    out = norm(spconv(out, sd["conv3.kernel"], g.down[1]), "norm3")   # :178-179
+    out_s4 = block(out, "block3", g.k3[2], g.levels[2][:, 0])
     out = F.relu(out_s4)
     tap("out_s4", out_s4)
-    out = batchnorm_eval(spconv(out, sd["conv4.kernel"], g.down[2]), sd, "norm4")   # :183-184
-    out_s8 = basic_block(out, sd, "block4", g.k3[3], g.levels[3][:, 0])
+    out = norm(spconv(out, sd["conv4.kernel"], g.down[2]), "norm4")   # :183-184
+    out_s8 = block(out, "block4", g.k3[3], g.levels[3][:, 0])
     out = F.relu(out_s8)
     tap("out_s8", out)
 
@@ -360,14 +375,14 @@ def resunet_forward(sd, coords, image, feats=None, normalize_feature=True,
     out = torch.cat(parts, 0)
     tap("fused", out)
 
-    out = batchnorm_eval(spconv(out, sd["conv4_tr.kernel"], g.up[2]), sd, "norm4_tr")
-    out = F.relu(basic_block(out, sd, "block4_tr", g.k3[2], g.levels[2][:, 0]))
+    out = norm(spconv(out, sd["conv4_tr.kernel"], g.up[2]), "norm4_tr")
+    out = F.relu(block(out, "block4_tr", g.k3[2], g.levels[2][:, 0]))
     out = torch.cat([out, out_s4], 1)                                     # ME.cat :197
-    out = batchnorm_eval(spconv(out, sd["conv3_tr.kernel"], g.up[1]), sd, "norm3_tr")
-    out = F.relu(basic_block(out, sd, "block3_tr", g.k3[1], g.levels[1][:, 0]))
+    out = norm(spconv(out, sd["conv3_tr.kernel"], g.up[1]), "norm3_tr")
+    out = F.relu(block(out, "block3_tr", g.k3[1], g.levels[1][:, 0]))
     out = torch.cat([out, out_s2], 1)                                     # :208
-    out = batchnorm_eval(spconv(out, sd["conv2_tr.kernel"], g.up[0]), sd, "norm2_tr")
-    out = F.relu(basic_block(out, sd, "block2_tr", g.k3[0], g.levels[0][:, 0]))
+    out = norm(spconv(out, sd["conv2_tr.kernel"], g.up[0]), "norm2_tr")
+    out = F.relu(block(out, "block2_tr", g.k3[0], g.levels[0][:, 0]))
     tap("out_s1_tr", out)
     out = torch.cat([out, out_s1], 1)                                     # :219
     out = F.relu(spconv(out, sd["conv1_tr.kernel"], None))                # :224-225
