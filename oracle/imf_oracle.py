@@ -121,14 +121,19 @@ def rulebook_transpose(coarse_coords, fine_coords, ts_fine, ksize):
     """Kernel map of MinkowskiConvolutionTranspose(k, stride 2) from tensor stride
     2*ts_fine to ts_fine: the forward (fine -> coarse) map with in/out
     swapped and the same k: out[f] += in[c] @ W[k] for f = c + off_k*ts_fine.
-    Returns nbr_t[f,k] = coarse row c or -1."""
+    Returns nbr_t[f,k] = coarse row c or -1 (a coordinate outside +-2^17 has no row, as in rulebook())."""
     offs = kernel_offsets(ksize) * ts_fine
     fine = np.asarray(fine_coords, np.int64)
     nbr = np.empty((len(fine), len(offs)), np.int32)
+    lim = (1 << (_BITS - 1))
     for k, o in enumerate(offs):
         q = fine.copy()
         q[:, 1:] -= o
-        nbr[:, k] = _lookup(coarse_coords, q)
+        ok = ((q[:, 1:] >= -lim) & (q[:, 1:] < lim)).all(axis=1)
+        q[~ok, 1:] = 0
+        r = _lookup(coarse_coords, q)
+        r[~ok] = -1
+        nbr[:, k] = r
     return nbr
 
 

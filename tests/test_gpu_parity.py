@@ -103,21 +103,7 @@ def test_pyramid_levels(ops, geom_s5):
         assert (cm.coords(ts).cpu().numpy() == g.levels[i]).all(), f"level {ts}"
 
 
-def _check_rulebook(rb, nbr_ref, identity_rows):
-    n_out, kvol = nbr_ref.shape
-    rows = rb.tile_rows.cpu().numpy()
-    nbr = rb.nbr.cpu().numpy().reshape(kvol, rb.n_slots)
-    valid = rows >= 0
-    assert sorted(rows[valid].tolist()) == list(range(n_out))
-    if identity_rows:
-        assert (rows[:n_out] == np.arange(n_out)).all()
-    assert (nbr[:, valid].T == nbr_ref[rows[valid]]).all()
-    assert (nbr[:, ~valid] == -1).all()
-    mask = rb.tile_mask.cpu().numpy().view(np.uint32).reshape(-1, 4)
-    act = (nbr.reshape(kvol, -1, 64) >= 0).any(axis=2)                   # [kvol, tiles]
-    for k in range(kvol):
-        assert (((mask[:, k // 32] >> (k % 32)) & 1).astype(bool) == act[k]).all()
-    return mask
+from geometry_restate import check_rulebook as _check_rulebook  # noqa: E402  (shared with test_gpu_geometry_exact.py)
 
 
 def test_rulebooks_conv(ops, geom_s5):
