@@ -97,6 +97,14 @@ k_rbs_keys(const int32_t *__restrict__ nbr, int kvol_rt, long long n_slots, long
 // count sit at the level's tail), so only ceil(valid / 1024) groups per wavefront are sorted; the padding of the last group
 // carries the largest key and, being behind every valid element, stays behind (stability) -- the first `valid` outputs are
 // exactly the valid slots.
+// k_rbs_window_sort's static LDS: ~132 KiB.  gfx950 has 160 KiB per workgroup, its predecessors 64 KiB (the Makefile's ARCH is
+// overridable): fail the build here, not the launch.
+constexpr size_t kSortLdsBytes = sizeof(unsigned) * (2 * kWindow + kSortWaves * kDigits + 2 * kDigits);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "k_rbs_window_sort keeps a 16 384-slot window in 132 KiB of LDS: build for gfx950 (160 KiB per workgroup)"
+#endif
+static_assert(kSortLdsBytes <= 160 * 1024, "k_rbs_window_sort: static LDS exceeds gfx950's 160 KiB per workgroup");
+
 __global__ void __launch_bounds__(kSortThreads)
 k_rbs_window_sort(const unsigned *__restrict__ keys, long long n_slots, long long n_out,
                   const int32_t *__restrict__ n_dev, int32_t *__restrict__ perm) {

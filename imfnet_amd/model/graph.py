@@ -22,6 +22,7 @@ import torch
 
 from .. import _lib
 from .._lib import DYN_WORDS, META_WORDS, FragmentCaps, FragmentIO, ImfError, MAX_BATCH, NetTrace, check
+from .plan import arm_trace, fp32_buffers, trace_records
 
 FLAG_NAMES = {1: "coordinate out of range", 2: "a level exceeded its row capacity", 4: "bounding box exceeds the bit grid",
               8: "an item has no voxel", 16: "far fewer rows than the capacity (split cover)"}
@@ -197,7 +198,7 @@ class _Bucket:
             io.events[i] = e if i < 11 or runner.diag_events else None
         io.side_stream, io.image_stream = runner.raw_streams(dev)
         io.trace = None
-        io.fp32_buffers = 1 if os.environ.get("IMFNET_FP32_BUFFERS") == "1" else 0   # (see model/plan.py)
+        io.fp32_buffers = fp32_buffers()
         self.graph = C.c_void_p()
         self.n_nodes = 0
         self.launches = 0
@@ -436,20 +437,15 @@ class FragmentRunner:
         """One fragment on `stream`: graph replay (captured on first use) or eager capacity-mode launches (always
         when `trace_list` is given: per-convolution HIP events are appended to it as ops.TRACE records).
         reuse_event: eager launches only -- this forward's head on the side stream (_Bucket.enqueue)."""
-        from .. import ops
-        from .plan import NativePlan, _RB
-        fp32_buffers = 1 if os.environ.get("IMFNET_FP32_BUFFERS") == "1" else 0
-        if b.io.fp32_buffers != fp32_buffers:         # the mode is part of a captured graph: capture again under the new one
-            b.io.fp32_buffers = fp32_buffers
+        if b.io.fp32_buffers != fp32_buffers():       # the mode is part of a captured graph: capture again under the new one
+            b.io.fp32_buffers = fp32_buffers()
             b.drop_graph()
         with torch.cuda.stream(stream):
             if trace_list is not None or not self.use_graph:
                 trace = evs = None
                 if trace_list is not None:
                     trace = (NetTrace * 23)()
-                    evs = [ops._Ev() for _ in range(23)]
-                    for i, e in enumerate(evs):
-                        trace[i].ev_begin, trace[i].ev_end, trace[i].launched = e.begin, e.end, 0
+                    evs = arm_trace(trace)
                 # imf_fragment_io.gpu_idle_hint: nothing of this runner's is still running (its last forward's end event has
                 # fired) -- a synchronous call; the executor then issues its side chain piecewise (LAB_NOTES 4g-11)
                 last = getattr(self, "_last_done", None)
@@ -479,18 +475,9 @@ class FragmentRunner:
         b.launches += 1
         res = FragmentResult(b, n_points, n_items, host, done, pooled=meta_to is None)
         if trace_list is not None:
-            arena = b.iarena.view(torch.int32)
-            for i, e in enumerate(evs):
-                t = trace[i]
-                if not t.launched:
-                    continue
-                rb = _RB(t.n_slots, t.n_out, t.kvol, t.kvol)
-                rb.nbr = t.nbr or 0
-                trace_list.append(dict(kernel=ops.conv_kernel_name(self.net_desc.conv[i].variant, t.cin, t.cout,
-                                                                   kernel_tag=t.kernel_tag),
-                                       kvol=t.kvol, cin=t.cin, cout=t.cout, rb=rb, split=t.split, ev=e,
-                                       name=NativePlan.ORDER[i], arena=arena, res=res, level=t.level,
-                                       slots_extra=t.slots_extra, kernel_tag=t.kernel_tag))
+            trace_list.extend(trace_records(
+                trace, evs, self.net_desc, b.iarena.view(torch.int32),
+                extra=lambda t: dict(res=res, level=t.level, slots_extra=t.slots_extra, kernel_tag=t.kernel_tag)))
         return res
 
     def run(self, xyz, item_starts, image, voxel, stream=None):

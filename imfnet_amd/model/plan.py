@@ -10,14 +10,13 @@ kernels, their order and their arithmetic are exactly those of the layer-at-a-ti
 (`tests/test_gpu_parity.py::test_fused_equals_layerwise` compares the two).
 """
 import ctypes as C
+import os
 
 import torch
 
 from .. import _lib, ops
 from .._lib import ConvArgs, ImfError, MASK_WORDS, TILE_ROWS, check
 
-
-import os
 _POISON = bool(os.environ.get("IMF_POISON"))
 
 
@@ -53,6 +52,34 @@ class _RB:
         self.nbr = base + 4 * self.n_slots
         self.tile_mask = self.nbr + 4 * self.kvol * self.n_slots
         return base + 4 * self.words()
+
+
+def fp32_buffers():
+    """IMFNET_FP32_BUFFERS=1: every feature buffer fp32 (the arithmetic of the op-by-op executor); default: the layers
+    hand split-f16 operand images on (include/imfnet_hip.h, imf_conv_args.operand_format)"""
+    return 1 if os.environ.get("IMFNET_FP32_BUFFERS") == "1" else 0
+
+
+def arm_trace(trace):
+    """A begin / end event pair for each record of a NetTrace array, nothing launched yet."""
+    evs = [ops._Ev() for _ in trace]
+    for t, e in zip(trace, evs):
+        t.ev_begin, t.ev_end, t.launched = e.begin, e.end, 0
+    return evs
+
+
+def trace_records(trace, evs, desc, arena, extra=None):
+    """ops.TRACE records of the launches imf_resunet_forward noted in `trace`; extra(t): further keys of a record."""
+    out = []
+    for i, (t, e) in enumerate(zip(trace, evs)):
+        if not t.launched:
+            continue
+        rb = _RB(t.n_slots, t.n_out, t.kvol, t.kvol)
+        rb.nbr = t.nbr or 0
+        out.append(dict(kernel=ops.conv_kernel_name(desc.conv[i].variant, t.cin, t.cout, kernel_tag=t.kernel_tag),
+                        kvol=t.kvol, cin=t.cin, cout=t.cout, rb=rb, split=t.split, ev=e, name=NativePlan.ORDER[i],
+                        arena=arena, **(extra(t) if extra else {})))
+    return out
 
 
 class FusedPlan:
@@ -416,27 +443,11 @@ class NativePlan:
         io.fusion_done = fusion_done.cuda_event
         io.side_stream, io.main_stream = side.cuda_stream, main.cuda_stream
         tracing = ops.TRACE is not None
-        if tracing:
-            evs = [ops._Ev() for _ in range(23)]
-            for i, e in enumerate(evs):
-                self._trace[i].ev_begin, self._trace[i].ev_end, self._trace[i].launched = e.begin, e.end, 0
-            io.trace = self._trace
-        else:
-            io.trace = None
+        evs = arm_trace(self._trace) if tracing else None
+        io.trace = self._trace if tracing else None
         io.flags = self.model.flag_word(dev).data_ptr()
-        # IMFNET_FP32_BUFFERS=1: every feature buffer fp32 (the arithmetic of the op-by-op executor); default: the layers
-        # hand split-f16 operand images on (include/imfnet_hip.h, imf_conv_args.operand_format)
-        io.fp32_buffers = 1 if os.environ.get("IMFNET_FP32_BUFFERS") == "1" else 0
+        io.fp32_buffers = fp32_buffers()
         check(L.imf_resunet_forward(C.byref(d), C.byref(io)), "imf_resunet_forward")
         if tracing:
-            for i, e in enumerate(evs):
-                t = self._trace[i]
-                if not t.launched:
-                    continue
-                rb = _RB(t.n_slots, t.n_out, t.kvol, t.kvol)
-                rb.nbr = t.nbr or 0
-                ops.TRACE.append(dict(kernel=ops.conv_kernel_name(d.conv[i].variant, t.cin, t.cout, kernel_tag=t.kernel_tag),
-                                      kvol=t.kvol,
-                                      cin=t.cin, cout=t.cout, rb=rb, split=t.split, ev=e, name=self.ORDER[i],
-                                      arena=iarena.view(torch.int32)))
+            ops.TRACE.extend(trace_records(self._trace, evs, d, iarena.view(torch.int32)))
         return F

@@ -66,6 +66,29 @@ def test_kernel_policy_is_static_per_layer_and_batch():
     assert tag(2, 27, 64, 64, 1, 2) == 0                                                 # other variants: no wave-split kernel
 
 
+def test_arena_sizes_equal_the_recorded_ones():
+    """imf_resunet_{int,float}_arena_bytes{,_cap}: callers allocate by them (tests/cabi/driver.cpp, model/graph.py), so the
+    byte counts are part of the ABI.  tests/golden/arena_bytes.json holds what the library returned BEFORE the executor's
+    arenas were laid out by one function (gen_arena_bytes.py, run on that commit's build): three descriptors (conv1 k5, k3,
+    and a 32-channel input that takes the rulebook first convolution) x six row-count sets from one row per level to the
+    benchmark's pair, exact mode without and with a bounding box, capacity mode with a 4-word and a 2^18-word bit grid."""
+    import ctypes
+    import importlib.util
+    from imfnet_amd import _lib
+    spec = importlib.util.spec_from_file_location("gen_arena_bytes", os.path.join(GOLDEN, "gen_arena_bytes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = json.load(open(os.path.join(GOLDEN, "arena_bytes.json")))
+    assert want["descs"] == gen.DESCS and tuple(want["bbox"]) == gen.BBOX
+    assert {(e["desc"], tuple(e["n"])) for e in want["entries"]} == {(d, r) for d in gen.DESCS for r in gen.ROWS}
+    assert (103396, 27011, 7013, 1907) in gen.ROWS and (63, 17, 5, 2) in gen.ROWS and len(gen.ROWS) == 6
+    got = gen.sizes(ctypes.CDLL(_lib.LIB_PATH))       # (a handle of its own: the generator sets plain-pointer signatures)
+    assert len(got) == len(want["entries"]) == 18
+    for g, w in zip(got, want["entries"]):
+        assert set(w["int_cap"]) == {"4", str(1 << 18)}
+        assert g == w, f"{w['desc']} n={w['n']}: {g} != recorded {w}"
+
+
 def test_kernel_tag_names_mirror_the_header():
     """The IMF_TAG_* constants of include/imfnet_hip.h, their mirror in _lib and the staging table of ops: the values are
     part of the ABI (bench.py reads 64 and 128 from trace records, C callers pass integers), so they are pinned here."""

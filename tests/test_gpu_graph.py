@@ -263,33 +263,64 @@ def test_strict_fp32_capacity_mode_equals_its_exact_mode(seeded_sd, clouds, imag
     assert np.abs(F_exact[:n0].cpu().numpy() - F_ref.numpy()).max() < 1e-4
 
 
-def test_side_chain_issue_order_does_not_change_the_descriptors(clouds):
+def test_side_chain_issue_order_does_not_change_the_descriptors(tmp_path):
     """imf_fragment_io.gpu_idle_hint (round 6): with nothing queued ahead the executor issues the side stream's pieces right
     before the first launch that waits for each, otherwise all of them ahead of conv1 -- same streams, same events, same order
     within each stream: the descriptors of a pair and of one fragment are the same bits either way (IMF_EAGER_SIDE forces the
-    order per call), and both equal the exact path."""
-    import bench
-    dev = torch.device("cuda:0")
-    model, _ = bench.build_model(dev)
-    pts, imgs = bench.load_pair(1.0)
-    old = os.environ.get("IMF_EAGER_SIDE")
-    try:
+    order; the switch is read once, so each setting runs in a process of its own), and both equal the exact path."""
+    import subprocess, sys, textwrap
+    code = textwrap.dedent("""
+        import os, sys, numpy as np, torch
+        sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests")); sys.path.insert(0, os.path.join(%r, "oracle"))
+        import bench
+        dev = torch.device("cuda:0")
+        model, _ = bench.build_model(dev)
+        pts, imgs = bench.load_pair(1.0)
         with torch.no_grad():
             for sel in ([0], [0, 1]):
                 wl = bench.Workload(model, dev, [pts[i] for i in sel], imgs[sel], 0.025)
                 F = wl.prepare_graph().clone()
                 wl.runner.use_graph = False
-                got = {}
-                for flag in ("1", "0"):
-                    os.environ["IMF_EAGER_SIDE"] = flag
-                    for _ in range(2):                                     # (twice: an idle GPU, then work queued ahead)
-                        r = wl.graph_step()
-                    torch.cuda.synchronize()
-                    assert r.flags == 0
-                    got[flag] = r.F.clone()
-                assert torch.equal(got["1"], got["0"]) and torch.equal(got["1"], F), sel
+                for _ in range(2):                                     # (twice: an idle GPU, then work queued ahead)
+                    r = wl.graph_step()
+                torch.cuda.synchronize()
+                assert r.flags == 0
+                np.save(os.path.join(sys.argv[1], "exact_%%d.npy" %% len(sel)), F.cpu().numpy())
+                np.save(os.path.join(sys.argv[1], "got_%%d.npy" %% len(sel)), r.F.cpu().numpy())
+        print("OK")
+    """) % (ROOT, ROOT, ROOT)
+    got = {}
+    for flag in ("1", "0"):
+        out = tmp_path / flag
+        out.mkdir()
+        p = subprocess.run([sys.executable, "-c", code, str(out)], env=dict(os.environ, IMF_EAGER_SIDE=flag),
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0 and "OK" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+        got[flag] = {n: torch.from_numpy(np.load(out / ("%s_%d.npy" % (n[0], n[1])))) for n in
+                     (("got", 1), ("exact", 1), ("got", 2), ("exact", 2))}
+    for n in (1, 2):
+        F = got["1"]["exact", n]
+        assert torch.equal(got["0"]["exact", n], F)
+        assert torch.equal(got["1"]["got", n], got["0"]["got", n]) and torch.equal(got["1"]["got", n], F), n
+
+
+def test_levels_below_one_tile_equal_in_every_executor(model, clouds, images):
+    """The arena layout at its edge (csrc/executor.hip, arena_layout): levels 2 and 3 smaller than one 64-row tile and no
+    row count a multiple of 64, so the padding terms of the layout (rows rounded up to 64, mask words per tile, the 256-byte
+    alignments) are no slack.  Native exact forward == the Python executor == capacity mode issued eagerly, bit for bit."""
+    pts = [clouds[0][:20000:8].astype(np.float64)]
+    F, inds, counts, bbox, items, coords = _exact(model, pts, images[0], 0.05)
+    assert 200 <= counts[0] < 1000 and counts[2] < 64 and counts[3] < 64 and all(c % 64 for c in counts), counts
+    os.environ["IMFNET_PYTHON_EXECUTOR"] = "1"
+    try:
+        F_py = _exact(model, pts, images[0], 0.05)[0]
     finally:
-        if old is None:
-            os.environ.pop("IMF_EAGER_SIDE", None)
-        else:
-            os.environ["IMF_EAGER_SIDE"] = old
+        del os.environ["IMFNET_PYTHON_EXECUTOR"]
+    assert torch.equal(F_py, F)
+    r = _runner(model)
+    r.use_graph = False
+    r.observe(len(pts[0]), counts, bbox)
+    xyz, starts = _cat(pts)
+    res = r.run(xyz, starts, torch.as_tensor(images[0]).to(DEV), 0.05, stream=torch.cuda.Stream())
+    assert res.flags == 0 and res.counts == counts and r.stats["eager"] == 1
+    assert torch.equal(res.F, F) and torch.equal(res.first_idx, inds)
