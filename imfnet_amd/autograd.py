@@ -12,6 +12,10 @@ MinkowskiEngine's autograd, lib/trainer.py:495-569).
   d kernel  imf_spconv_wgrad (csrc/backward.hip): per offset the sum of in[i]^T grad[o] over the map's pairs.
 Everything stays on the GPU; the maps come from the coordinate manager's cache (built once per fragment).
 
+`SparseBatchNormFunction` is the training-mode BatchNorm between them (csrc/norm_train.hip, ops.TRAIN_NORM == "hip"):
+fp64 batch statistics in a fixed order, the ReLU and the residual add of the residual block folded in, forward and
+backward; sparse.MinkowskiBatchNorm decides when it runs.
+
 Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
 two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
 range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
@@ -106,3 +110,40 @@ class SparseConvFunction(torch.autograd.Function):
             dw = spconv_wgrad(feat, g, rb, K)
             grad_kernel = dw if kernel.dim() == 3 else dw[0]
         return grad_feat, grad_kernel, None, None
+
+
+class SparseBatchNormFunction(torch.autograd.Function):
+    """y = [relu](batch_norm(x) [+ residual]) with batch statistics; `bn` is the nn.BatchNorm1d whose eps, momentum and
+    running statistics apply.  The running statistics and num_batches_tracked move exactly when torch moves them:
+    training mode with track_running_stats."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, bn, relu):
+        track = bn.training and bn.track_running_stats and bn.running_mean is not None
+        if track and bn.momentum is None:
+            raise ImfError("BatchNorm momentum=None (cumulative moving average) is not implemented by the hip norm "
+                           "kernels: use a momentum, or ops.TRAIN_NORM = 'torch'")
+        xc = x.detach().contiguous()
+        res = None if residual is None else residual.detach().contiguous()
+        y, stats = ops.bn_train_forward(xc, gamma.detach().contiguous(), beta.detach().contiguous(), bn.eps, res, relu,
+                                        bn.running_mean if track else None, bn.running_var if track else None,
+                                        bn.momentum if track else 0.0)
+        if track and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        ctx.save_for_backward(xc, y, stats, gamma)
+        ctx.relu = bool(relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y, stats, gamma = ctx.saved_tensors
+        need_x, need_g, need_b, need_r = ctx.needs_input_grad[:4]
+        g = grad_out.contiguous().float()
+        if not (need_x or need_g or need_b or need_r):
+            return None, None, None, None, None, None
+        # without a ReLU the residual's gradient is the incoming gradient itself: no copy
+        dx, dgamma, dbeta, dres = ops.bn_train_backward(g, x, y, stats, gamma.detach().contiguous(), ctx.relu, need_x,
+                                                        need_g, need_b, need_r and ctx.relu)
+        if need_r and not ctx.relu:
+            dres = g
+        return dx, dgamma, dbeta, dres, None, None

@@ -38,6 +38,11 @@ class BasicBlockBase(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        if isinstance(self.norm1, ME.MinkowskiBatchNorm):
+            # norm1 -> relu and norm2 -> + x -> relu, each ONE call: the same torch ops in the same order as below with
+            # ops.TRAIN_NORM == "torch", one HIP op each (csrc/norm_train.hip) with "hip" in training mode
+            y = self.conv2(self.norm1.forward_fused(self.conv1(x), relu=True))
+            return self.norm2.forward_fused(y, residual=x if self.downsample is None else self.downsample(x), relu=True)
         relu = ME.MinkowskiFunctional.relu
         y = relu(self.norm1(self.conv1(x)))
         y = self.norm2(self.conv2(y))

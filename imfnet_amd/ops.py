@@ -696,3 +696,81 @@ def fusion_attention(x, kt_packed, v_packed, n_tokens, tokens_padded, fw, out=No
     kernels); flags / variant as in `fusion_attention_batched`."""
     return fusion_attention_batched(x, [(0, x.shape[0])], [kt_packed], [v_packed], n_tokens, tokens_padded, fw, out=out,
                                     flags=flags, variant=variant)
+
+
+# Training-mode BatchNorm of the sparse path (env IMF_TRAIN_NORM; python -m imfnet_amd.train --norm_kernels):
+#   "torch" (default) = nn.BatchNorm1d, then the add, then F.relu: the op sequence sparse.MinkowskiBatchNorm always had;
+#   "hip"             = csrc/norm_train.hip through autograd.SparseBatchNormFunction: fp64 statistics in a fixed order,
+#                       ReLU and residual add folded in, bit-reproducible.  Used only in training mode under autograd on
+#                       fp32 GPU features with affine parameters; every other call runs the torch ops whatever the switch.
+TRAIN_NORM_CHOICES = ("torch", "hip")
+TRAIN_NORM = os.environ.get("IMF_TRAIN_NORM", "torch")
+if TRAIN_NORM not in TRAIN_NORM_CHOICES:
+    raise ImfError(f"IMF_TRAIN_NORM={TRAIN_NORM!r}: one of {', '.join(TRAIN_NORM_CHOICES)}")
+
+
+def set_train_norm(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_NORM
+    if name not in TRAIN_NORM_CHOICES:
+        raise ImfError(f"norm kernels {name!r}: one of {', '.join(TRAIN_NORM_CHOICES)}")
+    prev, TRAIN_NORM = TRAIN_NORM, name
+    return prev
+
+
+def bn_train_chunk_rows():
+    return _lib.lib().imf_bn_train_chunk_rows()
+
+
+def _bn_workspace(n, c, device):
+    nbytes = _lib.lib().imf_bn_train_workspace_bytes(n, c)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device), nbytes
+
+
+def _bn_rows(t, name, n, c):
+    _req(t, torch.float32, name, 2)
+    if tuple(t.shape) != (n, c):
+        raise ImfError(f"{name} must be [{n}, {c}], got {tuple(t.shape)}")
+    return t
+
+
+def bn_train_forward(x, gamma, beta, eps, residual=None, relu=False, running_mean=None, running_var=None, momentum=0.0):
+    """imf_bn_train_forward: (y [N, C] fp32, stats [2C] fp64 = batch mean, 1 / sqrt(biased variance + eps)).  The running
+    statistics, when given, are updated in place."""
+    _req(x, torch.float32, "x", 2)
+    n, c = x.shape
+    for name, t in (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and (_req(t, torch.float32, name, 1).shape[0] != c):
+            raise ImfError(f"{name} must be [{c}]")
+    if residual is not None:
+        _bn_rows(residual, "residual", n, c)
+    y = torch.empty_like(x)
+    stats = torch.empty(2 * c, dtype=torch.float64, device=x.device)
+    ws, nbytes = _bn_workspace(n, c, x.device)
+    check(_lib.lib().imf_bn_train_forward(x.data_ptr(), n, c, gamma.data_ptr(), beta.data_ptr(), float(eps), _ptr(residual),
+                                          int(bool(relu)), _ptr(running_mean), _ptr(running_var), float(momentum),
+                                          y.data_ptr(), stats.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "imf_bn_train_forward")
+    return y, stats
+
+
+def bn_train_backward(dy, x, y, stats, gamma, relu=False, want_dx=True, want_dgamma=True, want_dbeta=True,
+                      want_dresidual=False):
+    """imf_bn_train_backward: (dx, dgamma, dbeta, dresidual), None for each output that is not wanted.  y is read only
+    for the ReLU mask y > 0 (may be None when relu is false)."""
+    _req(dy, torch.float32, "dy", 2)
+    n, c = dy.shape
+    _bn_rows(x, "x", n, c)
+    if relu or y is not None:
+        _bn_rows(y, "y", n, c)
+    if _req(stats, torch.float64, "stats", 1).shape[0] != 2 * c or _req(gamma, torch.float32, "gamma", 1).shape[0] != c:
+        raise ImfError(f"stats must be [{2 * c}] and gamma [{c}]")
+    dx = torch.empty_like(x) if want_dx else None
+    dgamma = torch.empty_like(gamma) if want_dgamma else None
+    dbeta = torch.empty_like(gamma) if want_dbeta else None
+    dres = torch.empty_like(x) if want_dresidual else None
+    ws, nbytes = _bn_workspace(n, c, x.device)
+    check(_lib.lib().imf_bn_train_backward(dy.data_ptr(), x.data_ptr(), _ptr(y), int(bool(relu)), stats.data_ptr(),
+                                           gamma.data_ptr(), n, c, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dres),
+                                           ws.data_ptr(), nbytes, _stream()), "imf_bn_train_backward")
+    return dx, dgamma, dbeta, dres

@@ -320,7 +320,28 @@ class MinkowskiBatchNorm(nn.Module):
                                  track_running_stats=track_running_stats)
 
     def forward(self, x):
-        return x._like(self.bn(x.F))
+        return self.forward_fused(x)
+
+    def _hip_training(self, f):
+        """Whether this call runs on csrc/norm_train.hip: the switch, training mode, autograd, fp32 GPU rows, affine."""
+        return (ops.TRAIN_NORM == "hip" and self.bn.training and torch.is_grad_enabled() and f.is_cuda and
+                f.dtype == torch.float32 and f.dim() == 2 and self.bn.affine)
+
+    def forward_fused(self, x, residual=None, relu=False):
+        """relu(bn(x) + residual), the residual (a SparseTensor on x's map, or its feature matrix) and the ReLU optional.
+        With ops.TRAIN_NORM == "torch", and in every case the HIP op does not cover (eval mode, no_grad, no affine
+        parameters), the torch ops in the order the residual block always issued them: bn, then add, then relu."""
+        f = x.F
+        res = residual if residual is None or torch.is_tensor(residual) else residual.F
+        if self._hip_training(f):
+            from .autograd import SparseBatchNormFunction
+            return x._like(SparseBatchNormFunction.apply(f, self.bn.weight, self.bn.bias, res, self.bn, bool(relu)))
+        out = self.bn(f)
+        if res is not None:
+            out = out + res
+        if relu:
+            out = F.relu(out)
+        return x._like(out)
 
     def folded(self):
         """Eval-mode affine form y = x*scale + shift."""

@@ -107,6 +107,9 @@ def make_parser():
     a("--image_W", type=int, default=160)
     a("--image_H", type=int, default=120)
     a("--seed", type=int, default=0)
+    a("--norm_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="training-mode BatchNorm of the sparse path: torch ops, or the fused deterministic HIP kernels "
+           "(fp64 statistics, ReLU and residual add folded in)")
     return p
 
 
@@ -159,6 +162,8 @@ class HardestContrastiveTrainer:
         from ..model import load_model
         self.config = config
         self.device = torch.device(device)
+        from .. import ops
+        ops.set_train_norm(getattr(config, "norm_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)

@@ -973,6 +973,35 @@ int imf_spconv_wgrad(const float *in, int cin, const float *grad_out, int cout, 
                      const int32_t *nbr, int64_t n_slots, int64_t n_out, int kvol, float *dw /* [kvol][cin][cout] */,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Training-mode BatchNorm of the sparse path (csrc/norm_train.hip) --------------------------------------------------
+ * Replaces: ME.MinkowskiBatchNorm in training mode (nn.BatchNorm1d over the rows of the batched sparse tensor) and the
+ * ReLU / residual add that follow it in the residual block (model/residual_block.py:40-56), forward and backward.
+ * All features are row-major fp32 [n, c], any c >= 1; rows move as 16-byte vectors when c % 4 == 0 and the pointers are
+ * 16-byte aligned.  Batch statistics are fp64 sums over chunks of imf_bn_train_chunk_rows() rows (the cut depends on n
+ * only), chunk partials added in chunk order by one workgroup: no floating-point atomics, two calls give the same bits.
+ * Every call takes a stream and synchronises nothing.  Bad arguments (n < 2 -- torch refuses one value per channel in
+ * training mode, and so does this --, c < 1, a short workspace, a null required pointer) return IMF_EINVAL before any
+ * launch.  workspace: imf_bn_train_workspace_bytes(n, c), 8-byte aligned, for either call.
+ *
+ * forward:  stats[0..c) = batch mean, stats[c..2c) = 1 / sqrt(biased variance + eps), both fp64;
+ *           xh = fp32((double(x) - mean) * rstd);  y = fmaf(xh, gamma, beta) (+ residual) (then ReLU when relu != 0).
+ *           running_mean / running_var (fp32, either may be NULL) <- (1 - momentum) * old + momentum * new, with the
+ *           UNBIASED variance (* n / (n - 1)) as torch; computed in fp64 and rounded once.
+ *           Per element |y - exact| <= 4 * 2^-24 * (|gamma xh| + |beta| + |residual|), whatever |mean| / sigma.
+ * backward: g = dy, or 0 where relu != 0 and not y > 0;  dbeta = sum g;  dgamma = sum g * xh;
+ *           dx = gamma * rstd * (g - dbeta / n - xh * dgamma / n);  dresidual = g.  fp64 up to each fp32 store.
+ *           dx, dgamma, dbeta and dresidual may each be NULL: that output is not computed (no dx: no second pass; none of
+ *           dx / dgamma / dbeta: no reduction).  y may be NULL when relu == 0. */
+int imf_bn_train_chunk_rows(void);
+size_t imf_bn_train_workspace_bytes(int64_t n, int c);
+int imf_bn_train_forward(const float *x, int64_t n, int c, const float *gamma, const float *beta, double eps,
+                         const float *residual /* or NULL */, int relu, float *running_mean /* or NULL */,
+                         float *running_var /* or NULL */, double momentum, float *y, double *stats /* [2c] */,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int imf_bn_train_backward(const float *dy, const float *x, const float *y, int relu, const double *stats,
+                          const float *gamma, int64_t n, int c, float *dx, float *dgamma, float *dbeta, float *dresidual,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Host-side codecs of the batch path: HOST pointers, no GPU involved ----------------------
  * Replace what the reference does around every fragment with Open3D / matplotlib / OpenCV / numpy
  * (scripts/generate_desc.py:83-97,118-123, util/uio.py:33-40).  All return 0 / a count on success, a negative

@@ -15,7 +15,7 @@ radius_pairs at S25 (the fixture pair voxelised at 2.5 cm) and S50k (the fixture
 rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).query_ball_point(T src, r) on the host
 (one thread) for the same sets.
 
-Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--out FILE.json]
+Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -84,6 +84,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--norm_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -94,7 +95,8 @@ def main():
     with tempfile.TemporaryDirectory() as root:
         write_tree(root, clouds, images)
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
-                            "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out")])
+                            "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out"),
+                            "--norm_kernels", a.norm_kernels])
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -114,7 +116,7 @@ def main():
     for k in STAGES:
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
-    res.update(batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
+    res.update(norm_kernels=a.norm_kernels, batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
     ang = np.deg2rad(4.0)
     T[:3, :3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]]
