@@ -176,12 +176,14 @@ SIGNATURES = {
     "imf_bn_train_workspace_bytes": (_Z, [_L, _I]),
     "imf_bn_train_forward": (_I, [_P, _L, _I, _P, _P, _D, _P, _I, _P, _P, _D, _P, _P, _P, _Z, _P]),
     "imf_bn_train_backward": (_I, [_P, _P, _P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "imf_dam_heat": (_I, [_P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "imf_ply_vertex_count": (_L, [C.c_char_p]),
     "imf_ply_read_points": (_L, [C.c_char_p, _P, _L]),
     "imf_png_info": (_I, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_png_read_f32": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_png_read_u16": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_ply_write_points": (_I, [C.c_char_p, _P, _L]),
+    "imf_ply_write_points_rgb": (_I, [C.c_char_p, _P, _P, _L]),
     "imf_jpeg_info": (_I, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_jpeg_read_u8": (_I, [C.c_char_p, _P, _L, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "imf_resize_bilinear_f32": (_I, [_P, _I, _I, _I, _P, _I, _I, _I]),

@@ -451,6 +451,36 @@ int imf_ply_write_points(const char *path, const double *xyz, int64_t n) {
   });
 }
 
+/* Coloured points in the layout Open3D's write_point_cloud gives a cloud with colours (pytorch_dam/utils/image.py:162):
+ * binary little-endian, `double x, y, z` + `uchar red, green, blue` per vertex, 27 bytes each, Open3D's header comment.
+ * The file appears under its name only when it is complete (temporary file + rename). */
+int imf_ply_write_points_rgb(const char *path, const double *xyz, const uint8_t *rgb, int64_t n) {
+  return guarded<int>("imf_ply_write_points_rgb", [&]() -> int {
+  IMF_REQUIRE(path && ((xyz && rgb) || n == 0) && n >= 0 && n < (1ll << 31),
+              "imf_ply_write_points_rgb: path=%p xyz=%p rgb=%p n=%lld", (const void *)path, (const void *)xyz,
+              (const void *)rgb, (long long)n);
+  const std::string tmp = std::string(path) + ".tmp";
+  File fh(tmp.c_str(), "wb");
+  IMF_REQUIRE(fh.f, "imf_ply_write_points_rgb: cannot open %s (%s)", tmp.c_str(), strerror(errno));
+  fprintf(fh.f, "ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex %lld\n"
+                "property double x\nproperty double y\nproperty double z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", (long long)n);
+  constexpr size_t kRow = 3 * sizeof(double) + 3;
+  std::vector<unsigned char> body((size_t)n * kRow);
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    memcpy(&body[i * kRow], xyz + 3 * i, 3 * sizeof(double));
+    memcpy(&body[i * kRow + 3 * sizeof(double)], rgb + 3 * i, 3);
+  }
+  const bool wrote = fwrite(body.data(), 1, body.size(), fh.f) == body.size();
+  if (!(fh.close() && wrote) || rename(tmp.c_str(), path) != 0) {
+    remove(tmp.c_str());
+    set_error("imf_ply_write_points_rgb: cannot write %s (%s)", path, strerror(errno));
+    return IMF_EINVAL;
+  }
+  return IMF_OK;
+  });
+}
+
 /* cv2.resize(image, (W_out, H_out), INTER_LINEAR) for float images [H,W,C] -> [H_out,W_out,C]: bilinear with
  * half-pixel centres, edge clamp, no anti-aliasing (util/uio.py:33-40).  chw != 0 writes [C,H_out,W_out] (the
  * transposes of generate_desc.py:96-97 folded in). */

@@ -774,3 +774,36 @@ def bn_train_backward(dy, x, y, stats, gamma, relu=False, want_dx=True, want_dga
                                            gamma.data_ptr(), n, c, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dres),
                                            ws.data_ptr(), nbytes, _stream()), "imf_bn_train_backward")
     return dx, dgamma, dbeta, dres
+
+
+def dam_heat(out_prenorm, hidden, targets, accumulate=True, n_dev=None, heat=None):
+    """imf_dam_heat (csrc/dam.hip): Descriptor Activation Mapping of T target rows at once.  out_prenorm [N, 32] = the
+    output of `final` before normalisation, hidden [N, c_hid] = its input, targets int32 [T] on the device.  Returns
+    (heat [T, N] fp32, minmax [T, 2] fp32, flags [T] int32, weights [T, 32] fp32); flags[t] = 1 (and a zero heat row) for
+    a target outside the rows, with a zero or a non-finite pre-normalisation row.  n_dev (int32 [1]) caps the rows; `heat`
+    may be given to be written in place (rows beyond n_dev are left as they are)."""
+    _req(out_prenorm, torch.float32, "out_prenorm", 2)
+    _req(hidden, torch.float32, "hidden", 2)
+    _req(targets, torch.int32, "targets", 1)
+    n, c_out = out_prenorm.shape
+    c_hid = hidden.shape[1]
+    if hidden.shape[0] != n:
+        raise ImfError(f"hidden must have {n} rows, got {hidden.shape[0]}")
+    if c_out != 32 or c_hid < 32 or c_hid % 32:
+        raise ImfError(f"DAM supports c_out = 32 and c_hid a positive multiple of 32, got c_out={c_out} c_hid={c_hid}")
+    T = targets.shape[0]
+    if n_dev is not None:
+        _req(n_dev, torch.int32, "n_dev")
+    dev = out_prenorm.device
+    if heat is None:
+        heat = torch.empty((T, n), dtype=torch.float32, device=dev)
+    elif tuple(_req(heat, torch.float32, "heat", 2).shape) != (T, n):
+        raise ImfError(f"heat must be [{T}, {n}], got {tuple(heat.shape)}")
+    minmax = torch.zeros((T, 2), dtype=torch.float32, device=dev)
+    flags = torch.zeros(T, dtype=torch.int32, device=dev)
+    weights = torch.zeros((T, 32), dtype=torch.float32, device=dev)
+    if T:
+        check(_lib.lib().imf_dam_heat(out_prenorm.data_ptr(), n, _ptr(n_dev), hidden.data_ptr(), c_hid, c_out,
+                                      targets.data_ptr(), T, int(bool(accumulate)), weights.data_ptr(), heat.data_ptr(),
+                                      minmax.data_ptr(), flags.data_ptr(), _stream()), "imf_dam_heat")
+    return heat, minmax, flags, weights

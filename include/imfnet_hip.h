@@ -1002,6 +1002,23 @@ int imf_bn_train_backward(const float *dy, const float *x, const float *y, int r
                           const float *gamma, int64_t n, int c, float *dx, float *dgamma, float *dbeta, float *dresidual,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Descriptor Activation Mapping (csrc/dam.hip) ---------------------------------------------------------------------
+ * Replaces: pytorch_dam/base_dam.py:120-173 + pytorch_dam/dam.py:15-21 -- 32 backward passes through the whole network per
+ * target point, of which only final.kernel.grad is read -- by the closed form of that gradient, for T targets at once.
+ *   out_prenorm [n, 32] = the output of `final` before the L2 normalisation (bias included), 16-byte aligned;
+ *   hidden [n, c_hid]   = the input of `final`;  targets [T] = row indices, on the device;
+ *   r = |o[t]|, f = o[t] / r, a_j = 32 - j (accumulate != 0: the reference's accumulating .grad) or 1 (accumulate == 0);
+ *   w_c = mean_k(hidden[t, k]) * (a_c - f_c * sum_j a_j f_j) / r, fp64 sums in a fixed order, rounded once to fp32 and
+ *   left in weights [T, 32];  heat[t, i] = max(0, sum_c w_c * o[i, c]) as 32 fp32 FMAs over ascending c, heat [T, n]
+ *   (row stride n);  minmax[t] = (min, max) of heat[t, 0:rows), (0, 0) when there are no rows.
+ * n_dev (or NULL): device row count, rows = min(n, *n_dev); rows beyond it are neither read nor written.
+ * flags[t] = 1 and heat[t, :] = 0 when the target is outside [0, rows), r == 0 or r is not finite; else flags[t] = 0.
+ * No atomics: two calls give the same bits.  |heat - exact| <= 40 * 2^-24 * sum_c |w_c o[i, c]|.
+ * c_out must be 32 and c_hid a positive multiple of 32: IMF_EUNSUPPORTED otherwise.  T == 0 launches nothing. */
+int imf_dam_heat(const float *out_prenorm, int64_t n, const int32_t *n_dev, const float *hidden, int c_hid, int c_out,
+                 const int32_t *targets, int T, int accumulate, float *weights /* [T, 32] */, float *heat /* [T, n] */,
+                 float *minmax /* [T, 2] */, int32_t *flags /* [T] */, void *stream);
+
 /* ---- Host-side codecs of the batch path: HOST pointers, no GPU involved ----------------------
  * Replace what the reference does around every fragment with Open3D / matplotlib / OpenCV / numpy
  * (scripts/generate_desc.py:83-97,118-123, util/uio.py:33-40).  All return 0 / a count on success, a negative
@@ -1021,6 +1038,10 @@ int imf_png_read_u16(const char *path, uint16_t *out, int64_t capacity_samples, 
  * float32: the 3DMatch fragments' layout, which imf_ply_read_points reads).  Written through a temporary file and a
  * rename. */
 int imf_ply_write_points(const char *path, const double *xyz, int64_t n);
+/* Coloured points as Open3D writes them (o3d.io.write_point_cloud of a cloud with colours, pytorch_dam/utils/image.py:162):
+ * binary little-endian, `double x, y, z` + `uchar red, green, blue` per vertex, the header of files/3D_head_map.ply.
+ * Written through a temporary file and a rename. */
+int imf_ply_write_points_rgb(const char *path, const double *xyz, const uint8_t *rgb, int64_t n);
 
 /* matplotlib.image.imread of a .jpg (scripts/generate_desc.py:88-92: PIL = libjpeg's defaults, integer "islow" inverse DCT
  * and fancy chroma upsampling): uint8 [H, W, 3].  Baseline / extended sequential Huffman files with three YCbCr components in
