@@ -401,32 +401,31 @@ int first_convolution(const Forward &f, const Layout &l, Formats &fmt) {
   float *out = l.buf[ebuf(0, 0)];
   const int first_split = fmt.wants_split(ebuf(0, 0)) ? 1 : 0;
   bool wrote_split = first_split != 0;
+  ConvFirstArgs a{};
+  a.coords = l0.coords; a.n = s.n[0]; a.err = f.err; a.ksize = net->first_ksize; a.grid = l.bitgrid;
+  a.w = net->first_kernel; a.cout = s.ch[1]; a.scale = net->first_scale; a.shift = net->first_shift;
+  a.out = out; a.out_split = first_split;
+  if (f.dyn) {                       // capacity mode: row count and bounding box from the pyramid's meta block
+    a.n_dev = meta; a.bbox_dev = meta + kMetaBBox; a.grid_words = io->bitgrid_words;
+  } else {                           // exact size: the host box, where there is one and its grid is not too large
+    a.bbox = io->bbox;
+    if (io->x_all_ones && io->bbox && net->in_channels == 1) a.grid_words = imf_bitgrid_words(io->bbox, net->first_ksize);
+  }
   int rc;
-  if (f.first_and_map) {
-    rc = conv_first_and_map_dyn(l0.coords, s.n[0], meta, meta + kMetaBBox, f.err, net->first_ksize, l.bitgrid,
-                                io->bitgrid_words, net->first_kernel, s.ch[1], net->first_scale, net->first_shift, 0, out,
-                                first_split, l0.table, l0.capacity, l.k3[0].tile_rows, l.k3[0].nbr, l.k3[0].tile_mask, f.main,
-                                net->first_kernel_image);
-  } else if (f.dyn && f.pyr) {   // imf_fragment_forward zeroed the grid before the level-0 pyramid
-    rc = conv_first_bitgrid_dyn_cleared(l0.coords, s.n[0], meta, meta + kMetaBBox, f.err, net->first_ksize, l.bitgrid,
-                                        io->bitgrid_words, net->first_kernel, s.ch[1], net->first_scale, net->first_shift,
-                                        0, out, f.main, first_split, net->first_kernel_image);
-  } else if (f.dyn) {
-    rc = conv_first_bitgrid_dyn_fmt(l0.coords, s.n[0], meta, meta + kMetaBBox, f.err, net->first_ksize, l.bitgrid,
-                                    io->bitgrid_words, net->first_kernel, s.ch[1], net->first_scale, net->first_shift, 0,
-                                    out, f.main, first_split);
+  if (f.first_and_map) {             // ... with the level-0 3x3x3 map from the same launch
+    a.grid_filled = true; a.w_image = net->first_kernel_image;
+    a.table = l0.table; a.capacity = l0.capacity;
+    a.tile_rows = l.k3[0].tile_rows; a.nbr = l.k3[0].nbr; a.tile_mask = l.k3[0].tile_mask;
+  } else if (f.dyn && f.pyr) {       // imf_fragment_forward zeroed the grid before the level-0 pyramid, which set the bits
+    a.grid_filled = true; a.w_image = net->first_kernel_image;
+  }
+  if (f.dyn || a.grid_words) {
+    rc = conv_first_bitgrid(a, f.main);
   } else {
-    size_t words = 0;
-    if (io->x_all_ones && io->bbox && net->in_channels == 1) words = imf_bitgrid_words(io->bbox, net->first_ksize);
-    if (words) {
-      rc = conv_first_bitgrid_flags_fmt(l0.coords, s.n[0], io->bbox, net->first_ksize, l.bitgrid, words, net->first_kernel,
-                                        s.ch[1], net->first_scale, net->first_shift, 0, out, f.err, f.main, first_split);
-    } else {
-      rc = imf_conv_first_fused(l0.table, l0.capacity, l0.coords, s.n[0], 1, net->first_ksize,
-                                io->x_all_ones ? nullptr : io->x, net->in_channels, net->first_kernel, s.ch[1],
-                                net->first_scale, net->first_shift, 0, out, f.main);
-      wrote_split = false;   // (the hash-probing first layer writes fp32)
-    }
+    rc = imf_conv_first_fused(l0.table, l0.capacity, l0.coords, s.n[0], 1, net->first_ksize,
+                              io->x_all_ones ? nullptr : io->x, net->in_channels, net->first_kernel, s.ch[1],
+                              net->first_scale, net->first_shift, 0, out, f.main);
+    wrote_split = false;   // (the hash-probing first layer writes fp32)
   }
   if (rc) return rc;
   fmt.is_split[ebuf(0, 0)] = wrote_split;

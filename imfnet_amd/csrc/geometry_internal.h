@@ -5,7 +5,7 @@
 
 namespace imf {
 
-// ---- conv1's occupancy bit grid (spconv.hip: k_conv_first_bits; geometry.hip: filled by the level-0 compaction) ----
+// ---- conv1's occupancy bit grid (conv_first.hip: k_conv_first_bits; geometry.hip: filled by the level-0 compaction) ----
 struct GridDesc {
   int b0, x0, y0, z0;      // origin (bounding-box min minus the kernel radius)
   int nb, nx, ny, nz;      // extent in voxels (margins included)
@@ -31,7 +31,7 @@ struct DynGrid {
   const int32_t *n_dev, *bbox_dev;
   int32_t *err;
   unsigned long long words_cap;
-  const float *w_image = nullptr;   // conv1's hi / lo f16 weight image (imf_pack_first_kernel), or NULL: split in the kernel
+  const float *w_image = nullptr;   // conv1's three-part f16 weight image (imf_pack_first_kernel), or NULL: split in the kernel
 };
 
 __device__ __forceinline__ bool dyn_grid(const DynGrid &d, int ksize, GridDesc &g, long long &n) {

@@ -1,4 +1,4 @@
-// The neighbour-map builder's per-tile body (geometry.hip: k_rulebook; spconv.hip: the launch that builds the level-0
+// The neighbour-map builder's per-tile body (geometry.hip: k_rulebook; conv_first.hip: the launch that builds the level-0
 // 3x3x3 map beside conv1).
 #pragma once
 #include "common.h"

@@ -1,4 +1,4 @@
-// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_g.hip, spconv_w.hip).
+// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_g.hip, spconv_w.hip, conv_first.hip).
 #pragma once
 #include "common.h"
 
@@ -379,7 +379,6 @@ void launch_spconv_g(const ConvParams &p, dim3 grid, int co_blk, hipStream_t st,
 // imf_conv_args.kernel_tag as the caller gave it (IMF_TAG_WAVE8 or IMF_TAG_WAVE4 set); `tiles` = 64-row tiles of the map
 void launch_spconv_w(const ConvParams &p, unsigned tiles, int tag, hipStream_t st);
 
-// spconv.hip: imf_conv_first_bitgrid_dyn on a grid the caller already zeroed and filled (geometry.hip: k_emit_unique)
 // the fusion block with its output optionally written as a split-f16 operand image (fusion.hip; for imf_resunet_forward)
 int fusion_attention_dyn_fmt(const float *x, int64_t n_cap, const int32_t *n_dev, const int32_t *item_starts_dev,
                              int n_items, int32_t *err, const float *const *kt_packed, const float *const *v_packed,
@@ -390,21 +389,32 @@ int fusion_attention_batched_fmt(const float *x, int n_items, const int64_t *ite
                                  int tokens_padded, const imf_fusion_weights *w, float scale, float *out,
                                  void *workspace, size_t workspace_bytes, int32_t *flags, void *stream, int out_split,
                                  int variant = 6);
-int conv_first_bitgrid_flags_fmt(const int32_t *coords, int64_t n, const int32_t *bbox, int ksize, uint32_t *grid,
-                                 size_t grid_words, const float *w, int cout, const float *scale, const float *shift,
-                                 int relu, float *out, int32_t *flags, hipStream_t stream, int out_split);
-int conv_first_bitgrid_dyn_fmt(const int32_t *coords, int64_t n_cap, const int32_t *n_dev, const int32_t *bbox_dev,
-                               int32_t *err, int ksize, uint32_t *grid, size_t grid_words, const float *w, int cout,
-                               const float *scale, const float *shift, int relu, float *out, hipStream_t stream,
-                               int out_split);
-int conv_first_and_map_dyn(const int32_t *coords, int64_t n_cap, const int32_t *n_dev, const int32_t *bbox_dev, int32_t *err,
-                           int ksize, uint32_t *grid, size_t grid_words, const float *w, int cout, const float *scale,
-                           const float *shift, int relu, float *out, int out_split, const imf_slot *table, int64_t capacity,
-                           int32_t *tile_rows, int32_t *nbr, uint32_t *tile_mask, hipStream_t st,
-                           const float *w_image = nullptr);
-int conv_first_bitgrid_dyn_cleared(const int32_t *coords, int64_t n_cap, const int32_t *n_dev, const int32_t *bbox_dev,
-                                   int32_t *err, int ksize, uint32_t *grid, size_t grid_words, const float *w, int cout,
-                                   const float *scale, const float *shift, int relu, float *out, hipStream_t stream,
-                                   int out_split = 0, const float *w_image = nullptr);
+
+// conv_first.hip: conv1 of the all-ones feature on its occupancy bit grid -- the one launch path behind the public
+// imf_conv_first_bitgrid* entry points and the executor.  Zero-initialise, then set what the route needs.
+struct ConvFirstArgs {
+  const int32_t *coords;          // level-0 rows
+  int64_t n;                      // their count, or their capacity when n_dev is set
+  const int32_t *bbox;            // [host] bounding box: exact-size launch.  NULL: capacity mode, with
+  const int32_t *n_dev, *bbox_dev;   // the row count and the box on the device (the meta block of imf_pyramid_build)
+  int32_t *err;                   // flag word (IMF_FLAG_BITGRID, IMF_FLAG_RANGE); optional in exact-size mode
+  int ksize;
+  uint32_t *grid;
+  size_t grid_words;
+  bool grid_filled;               // the caller zeroed the grid and set the bits (k_emit_unique): no memset, no k_bitgrid_fill
+  const float *w, *w_image;       // the kernel [ksize^3, 1, cout]; optionally its image from imf_pack_first_kernel
+  int cout;
+  const float *scale, *shift;
+  int relu;
+  float *out;
+  int out_split;                  // write `out` as a split-f16 operand image (ConvParams::a_split of block1)
+  // the level-0 3x3x3 neighbour map (as imf_rulebook_conv_dyn, tensor stride 1) from the same launch: all set =
+  // k_conv_first_and_map (capacity mode on a filled grid only), all NULL = k_conv_first_bits
+  const imf_slot *table;
+  int64_t capacity;
+  int32_t *tile_rows, *nbr;
+  uint32_t *tile_mask;
+};
+int conv_first_bitgrid(const ConvFirstArgs &a, hipStream_t st);
 
 }  // namespace imf

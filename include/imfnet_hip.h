@@ -419,8 +419,9 @@ int imf_conv_first_fused(const imf_slot *table, int64_t capacity,
 /* First-layer convolution for the all-ones occupancy feature (util/misc.py:76-79) on a dense
  * occupancy BIT GRID over the level's bounding box (bbox [host] = min b,x,y,z, max b,x,y,z as
  * imf_pyramid_build reports it): 25 five-bit windows per voxel instead of 125 hash probes, then
- * out = occupancy . W on fp32 MFMA.  grid: caller scratch of >= imf_bitgrid_words(bbox, ksize)
- * uint32 words (0 = box too large: use imf_conv_first_fused).  Tensor stride 1.
+ * out = occupancy . W on the f16 matrix pipe with exact three-part weights (fp32 arithmetic).
+ * grid: caller scratch of >= imf_bitgrid_words(bbox, ksize) uint32 words (0 = box too large: use
+ * imf_conv_first_fused).  Tensor stride 1.
  * Replaces: conv1 + norm1 of model/resunet.py:42-49,168-169 (kernel map included). */
 size_t imf_bitgrid_words(const int32_t *bbox /* [host] */, int ksize);
 int imf_conv_first_bitgrid(const int32_t *coords, int64_t n, const int32_t *bbox /* [host] */, int ksize,

@@ -136,6 +136,98 @@ def test_first_conv_counts_exactly_the_occupied_offsets(ops, name, ks):
         assert bits is not None and np.array_equal(bits.cpu().numpy(), want)
 
 
+class _BitGrid:
+    """conv1's public bit-grid entry points called straight through the C ABI on the level-0 rows of a case."""
+    SENTINEL = -12345.0
+
+    def __init__(self, ops, name, ks, cout, kernel_scale=1.0):
+        from imfnet_amd import _lib
+        self.lib, self.L, self.ks, self.cout = _lib, _lib.lib(), ks, cout
+        rows, _, g, _ = _expected(name)
+        self.levels, _ = _build(ops, name)                       # (kept: the arena owns the coordinate rows)
+        self.coords, self.n = self.levels[0].coords.contiguous(), self.levels[0].n      # int32 [n, 4]
+        w = R.int_kernel(ks, cout) * np.float32(kernel_scale)
+        self.want = R.first_conv_expected(g.k_first if ks == 5 else g.k3[0], w).astype(np.float32)
+        self.w = torch.as_tensor(w).to(DEV)
+        self.bbox = [int(v) for v in self.levels[0].bbox]
+        assert self.coords.shape == (len(rows), 4) and self.bbox == R.bbox(rows)
+        self.box = (C.c_int32 * 8)(*self.bbox)
+        self.words = int(self.L.imf_bitgrid_words(self.box, ks))
+        assert self.words > 0
+        self.st = torch.cuda.current_stream().cuda_stream
+
+    def _grid(self, words):
+        return torch.full((words,), -1, dtype=torch.int32, device=DEV)          # (all bits set: the launch must clear it)
+
+    def plain(self):
+        grid, out = self._grid(self.words), torch.full((self.n, self.cout), self.SENTINEL, device=DEV)
+        self.lib.check(self.L.imf_conv_first_bitgrid(self.coords.data_ptr(), self.n, self.box, self.ks, grid.data_ptr(), self.words,
+                                                     self.w.data_ptr(), self.cout, None, None, 0, out.data_ptr(), self.st),
+                       "imf_conv_first_bitgrid")
+        return out.cpu().numpy()
+
+    def flags(self):
+        grid, out = self._grid(self.words), torch.full((self.n, self.cout), self.SENTINEL, device=DEV)
+        word = torch.zeros(1, dtype=torch.int32, device=DEV)
+        self.lib.check(self.L.imf_conv_first_bitgrid_flags(self.coords.data_ptr(), self.n, self.box, self.ks, grid.data_ptr(),
+                                                           self.words, self.w.data_ptr(), self.cout, None, None, 0, out.data_ptr(),
+                                                           word.data_ptr(), self.st), "imf_conv_first_bitgrid_flags")
+        return out.cpu().numpy(), int(word.item())
+
+    def dyn(self, grid_words=None):
+        """(out [n_cap, cout], err): capacity mode, n_cap = n + 70 rows, the row count and the box on the device."""
+        words = self.words if grid_words is None else grid_words
+        n_cap = self.n + 70
+        coords = torch.zeros((n_cap, 4), dtype=torch.int32, device=DEV)
+        coords[: self.n] = self.coords
+        n_dev = torch.tensor([self.n], dtype=torch.int32, device=DEV)
+        bbox_dev = torch.tensor(self.bbox, dtype=torch.int32, device=DEV)
+        err = torch.zeros(1, dtype=torch.int32, device=DEV)
+        grid, out = self._grid(words), torch.full((n_cap, self.cout), self.SENTINEL, device=DEV)
+        self.lib.check(self.L.imf_conv_first_bitgrid_dyn(coords.data_ptr(), n_cap, n_dev.data_ptr(), bbox_dev.data_ptr(),
+                                                         err.data_ptr(), self.ks, grid.data_ptr(), words, self.w.data_ptr(),
+                                                         self.cout, None, None, 0, out.data_ptr(), self.st),
+                       "imf_conv_first_bitgrid_dyn")
+        return out.cpu().numpy(), int(err.item())
+
+
+@pytest.mark.parametrize("cout", [32, 64])
+@pytest.mark.parametrize("ks", [3, 5])
+@pytest.mark.parametrize("name", ("n63", "n64", "n65", "solid", "batched2"))
+def test_every_public_bitgrid_entry_counts_exactly(ops, name, ks, cout):
+    """imf_conv_first_bitgrid, _flags and _dyn through the C ABI, both kernel sizes and both widths, against the integer
+    expectation: one 64-row block and its partial-block edge (n63 / n64 / n65), windows that straddle 32-bit grid words
+    (solid), a grid origin b0 over two items (batched2).  Capacity mode leaves the rows beyond the count untouched."""
+    b = _BitGrid(ops, name, ks, cout)
+    assert np.array_equal(b.plain(), b.want)
+    out, word = b.flags()
+    assert np.array_equal(out, b.want) and word == 0
+    out, err = b.dyn()
+    assert err == 0
+    assert np.array_equal(out[: b.n], b.want)
+    assert (out[b.n:] == b.SENTINEL).all()
+
+
+def test_bitgrid_flags_reports_the_f16_range(ops):
+    """The integer kernel times 2^14: channel 0 of an interior row of `solid` is sum(k + 1) * 2^14 >= 65504, so
+    IMF_FLAG_RANGE (32) must be raised -- and the output is still exact: a power-of-two scale keeps the three-part split of
+    the weights exact."""
+    b = _BitGrid(ops, "solid", 5, 32, kernel_scale=2.0 ** 14)
+    assert b.want[:, 0].max() == 125 * 126 // 2 * 2 ** 14 >= 65504
+    out, word = b.flags()
+    assert word & 32
+    assert np.array_equal(out, b.want)
+
+
+def test_bitgrid_dyn_declines_a_grid_one_word_short(ops):
+    """imf_conv_first_bitgrid_dyn with one grid word fewer than the box needs: IMF_FLAG_BITGRID (4) and the launch does
+    nothing -- every output row is still the sentinel."""
+    b = _BitGrid(ops, "n65", 5, 32)
+    out, err = b.dyn(grid_words=b.words - 1)
+    assert err & 4
+    assert (out == b.SENTINEL).all()
+
+
 # ------------------------------------------------------------------------------------------------ capacity mode
 class _Rb:
     def __init__(self, tile_rows, nbr, tile_mask, n_slots):

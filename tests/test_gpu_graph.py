@@ -324,3 +324,15 @@ def test_levels_below_one_tile_equal_in_every_executor(model, clouds, images):
     res = r.run(xyz, starts, torch.as_tensor(images[0]).to(DEV), 0.05, stream=torch.cuda.Stream())
     assert res.flags == 0 and res.counts == counts and r.stats["eager"] == 1
     assert torch.equal(res.F, F) and torch.equal(res.first_idx, inds)
+    # The same bucket with every stream collapsed onto the main one (io.serialize): side == main, so conv1 is not paired
+    # with the level-0 map (k_conv_first_and_map above) but runs alone on the grid the pyramid filled (k_conv_first_bits).
+    torch.cuda.synchronize()
+    res.bucket.out.zero_()                                        # (res.F is a view of it: nothing of the first run is left)
+    torch.cuda.synchronize()
+    res.bucket.io.serialize = 1
+    try:
+        res1 = r.run(xyz, starts, torch.as_tensor(images[0]).to(DEV), 0.05, stream=torch.cuda.Stream())
+        assert res1.bucket is res.bucket and r.stats["eager"] == 2
+        assert res1.flags == 0 and res1.counts == counts and torch.equal(res1.F, F)
+    finally:
+        res.bucket.io.serialize = 0
