@@ -176,6 +176,11 @@ SIGNATURES = {
     "imf_bn_train_workspace_bytes": (_Z, [_L, _I]),
     "imf_bn_train_forward": (_I, [_P, _L, _I, _P, _P, _D, _P, _I, _P, _P, _D, _P, _P, _P, _Z, _P]),
     "imf_bn_train_backward": (_I, [_P, _P, _P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "imf_hc_loss_workspace_bytes": (_Z, [_L, _L, _I, _L, _L, _L, _L]),
+    "imf_hc_loss_forward": (_I, [_P, _L, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _D, _D, _P, _P, _P, _P, _P, _P, _P,
+                                 _Z, _P]),
+    "imf_hc_loss_backward": (_I, [_P, _L, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _D, _D, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _Z, _P]),
     "imf_dam_heat": (_I, [_P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "imf_ply_vertex_count": (_L, [C.c_char_p]),
     "imf_ply_read_points": (_L, [C.c_char_p, _P, _L]),

@@ -16,6 +16,10 @@ Everything stays on the GPU; the maps come from the coordinate manager's cache (
 fp64 batch statistics in a fixed order, the ReLU and the residual add of the residual block folded in, forward and
 backward; sparse.MinkowskiBatchNorm decides when it runs.
 
+`HardestContrastiveLossFunction` is the loss at the end (csrc/loss.hip, ops.TRAIN_LOSS == "hip"): both losses, the
+hardest negatives and the closed-form gradient with respect to the two feature matrices, fp64 sums in a fixed order;
+train.loss.hardest_contrastive_loss decides when it runs.
+
 Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
 two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
 range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
@@ -147,3 +151,34 @@ class SparseBatchNormFunction(torch.autograd.Function):
         if need_r and not ctx.relu:
             dres = g
         return dx, dgamma, dbeta, dres, None, None
+
+
+class HardestContrastiveLossFunction(torch.autograd.Function):
+    """(pos_loss, neg_loss, hard01, hard10) of csrc/loss.hip (ops.TRAIN_LOSS == "hip"): the two losses as 0-d device
+    tensors, the hardest negatives as global rows (int64, not differentiable).  pairs / pos_sel / sel0 / sel1 are int64
+    device tensors (pos_sel None: every pair).  The backward hands the two incoming gradients to the kernels as one
+    2-element device tensor; nothing on either way waits for the device."""
+
+    @staticmethod
+    def forward(ctx, F0, F1, pairs, pos_sel, sel0, sel1, pos_thresh, neg_thresh):
+        f0, f1 = F0.detach().float().contiguous(), F1.detach().float().contiguous()
+        loss, hard01, hard10, keep01, keep10, meta = ops.hc_loss_forward(f0, f1, pairs, pos_sel, sel0, sel1, pos_thresh,
+                                                                         neg_thresh)
+        ctx.save_for_backward(f0, f1, pairs, pos_sel, sel0, sel1, hard01, hard10, keep01, keep10, meta)
+        ctx.thresh = (float(pos_thresh), float(neg_thresh))
+        ctx.dtypes = (F0.dtype, F1.dtype)
+        ctx.mark_non_differentiable(hard01, hard10)
+        return loss[0], loss[1], hard01, hard10
+
+    @staticmethod
+    def backward(ctx, grad_pos, grad_neg, _g01, _g10):
+        f0, f1, pairs, pos_sel, sel0, sel1, hard01, hard10, keep01, keep10, meta = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 8
+        zero = f0.new_zeros(())
+        grad = torch.stack([zero if grad_pos is None else grad_pos.float().reshape(()),
+                            zero if grad_neg is None else grad_neg.float().reshape(())]).contiguous()
+        df0, df1 = ops.hc_loss_backward(f0, f1, pairs, pos_sel, sel0, sel1, *ctx.thresh, hard01, hard10, keep01, keep10,
+                                        meta, grad)
+        return (df0.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
+                df1.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)

@@ -776,6 +776,90 @@ def bn_train_backward(dy, x, y, stats, gamma, relu=False, want_dx=True, want_dga
     return dx, dgamma, dbeta, dres
 
 
+# The hardest-contrastive loss of training (env IMF_TRAIN_LOSS; python -m imfnet_amd.train --loss_kernels):
+#   "torch" (default) = the torch ops of train/loss.py around two imf_nn_search calls, differentiated by torch's autograd;
+#   "hip"             = csrc/loss.hip through autograd.HardestContrastiveLossFunction: fp64 terms summed in a fixed order,
+#                       forward and backward, no floating-point atomics, no host wait, bit-reproducible.
+TRAIN_LOSS_CHOICES = ("torch", "hip")
+TRAIN_LOSS = os.environ.get("IMF_TRAIN_LOSS", "torch")
+if TRAIN_LOSS not in TRAIN_LOSS_CHOICES:
+    raise ImfError(f"IMF_TRAIN_LOSS={TRAIN_LOSS!r}: one of {', '.join(TRAIN_LOSS_CHOICES)}")
+
+
+def set_train_loss(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_LOSS
+    if name not in TRAIN_LOSS_CHOICES:
+        raise ImfError(f"loss kernels {name!r}: one of {', '.join(TRAIN_LOSS_CHOICES)}")
+    prev, TRAIN_LOSS = TRAIN_LOSS, name
+    return prev
+
+
+def _hc_args(f0, f1, pairs, pos_sel, sel0, sel1):
+    """Dtypes, shapes and devices of the loss's inputs (not the index values); the sizes and the workspace."""
+    _req(f0, torch.float32, "f0", 2)
+    _req(f1, torch.float32, "f1", 2)
+    _req(pairs, torch.int64, "pairs", 2)
+    _req(sel0, torch.int64, "sel0", 1)
+    _req(sel1, torch.int64, "sel1", 1)
+    if pos_sel is not None:
+        _req(pos_sel, torch.int64, "pos_sel", 1)
+    c = f0.shape[1]
+    if f1.shape[1] != c or pairs.shape[1] != 2:
+        raise ImfError(f"f1 must be [n1, {c}] and pairs [n_pairs, 2], got {tuple(f1.shape)} and {tuple(pairs.shape)}")
+    for name, t in (("f1", f1), ("pairs", pairs), ("sel0", sel0), ("sel1", sel1), ("pos_sel", pos_sel)):
+        if t is not None and t.device != f0.device:
+            raise ImfError(f"{name} is on {t.device}, f0 on {f0.device}")
+    n_pairs = pairs.shape[0]
+    n_pos = n_pairs if pos_sel is None else pos_sel.shape[0]
+    sizes = (f0.shape[0], f1.shape[0], c, n_pairs, n_pos, sel0.shape[0], sel1.shape[0])
+    nbytes = _lib.lib().imf_hc_loss_workspace_bytes(*sizes)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=f0.device)
+    return sizes, ws, nbytes
+
+
+def _hc_call(fn, f0, f1, pairs, pos_sel, sel0, sel1, sizes, pos_thresh, neg_thresh, rest, ws, nbytes):
+    n0, n1, c, n_pairs, n_pos, n_sel0, n_sel1 = sizes
+    return fn(f0.data_ptr(), n0, f1.data_ptr(), n1, c, pairs.data_ptr(), n_pairs, _ptr(pos_sel), n_pos, sel0.data_ptr(),
+              n_sel0, sel1.data_ptr(), n_sel1, float(pos_thresh), float(neg_thresh), *[t.data_ptr() for t in rest],
+              ws.data_ptr(), nbytes, _stream())
+
+
+def hc_loss_forward(f0, f1, pairs, pos_sel, sel0, sel1, pos_thresh, neg_thresh):
+    """imf_hc_loss_forward: (loss fp32 [2] = (pos_loss, neg_loss), hard01, hard10 int64 [n_pos], keep01, keep10 uint8
+    [n_pos], meta int32 [4] = (count of keep01, count of keep10, flags, 0)), all on the device; nothing waits for it.
+    pos_sel None takes every pair in order."""
+    sizes, ws, nbytes = _hc_args(f0, f1, pairs, pos_sel, sel0, sel1)
+    n_pos, dev = sizes[4], f0.device
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    hard01 = torch.empty(n_pos, dtype=torch.int64, device=dev)
+    hard10 = torch.empty(n_pos, dtype=torch.int64, device=dev)
+    keep01 = torch.empty(n_pos, dtype=torch.uint8, device=dev)
+    keep10 = torch.empty(n_pos, dtype=torch.uint8, device=dev)
+    meta = torch.empty(4, dtype=torch.int32, device=dev)
+    check(_hc_call(_lib.lib().imf_hc_loss_forward, f0, f1, pairs, pos_sel, sel0, sel1, sizes, pos_thresh, neg_thresh,
+                   (loss, hard01, hard10, keep01, keep10, meta), ws, nbytes), "imf_hc_loss_forward")
+    return loss, hard01, hard10, keep01, keep10, meta
+
+
+def hc_loss_backward(f0, f1, pairs, pos_sel, sel0, sel1, pos_thresh, neg_thresh, hard01, hard10, keep01, keep10, meta,
+                     grad, df0=None, df1=None):
+    """imf_hc_loss_backward: (df0, df1) for the upstream gradients grad fp32 [2] (of pos_loss, neg_loss) on the device.
+    df0 / df1 may be given; they are written whole."""
+    sizes, ws, nbytes = _hc_args(f0, f1, pairs, pos_sel, sel0, sel1)
+    n_pos = sizes[4]
+    for name, t, dtype, n in (("hard01", hard01, torch.int64, n_pos), ("hard10", hard10, torch.int64, n_pos),
+                              ("keep01", keep01, torch.uint8, n_pos), ("keep10", keep10, torch.uint8, n_pos),
+                              ("meta", meta, torch.int32, 4), ("grad", grad, torch.float32, 2)):
+        if _req(t, dtype, name, 1).shape[0] != n or t.device != f0.device:
+            raise ImfError(f"{name} must be [{n}] on {f0.device}")
+    df0 = torch.empty_like(f0) if df0 is None else _bn_rows(df0, "df0", *f0.shape)
+    df1 = torch.empty_like(f1) if df1 is None else _bn_rows(df1, "df1", *f1.shape)
+    check(_hc_call(_lib.lib().imf_hc_loss_backward, f0, f1, pairs, pos_sel, sel0, sel1, sizes, pos_thresh, neg_thresh,
+                   (hard01, hard10, keep01, keep10, meta, grad, df0, df1), ws, nbytes), "imf_hc_loss_backward")
+    return df0, df1
+
+
 def dam_heat(out_prenorm, hidden, targets, accumulate=True, n_dev=None, heat=None):
     """imf_dam_heat (csrc/dam.hip): Descriptor Activation Mapping of T target rows at once.  out_prenorm [N, 32] = the
     output of `final` before normalisation, hidden [N, c_hid] = its input, targets int32 [T] on the device.  Returns

@@ -16,6 +16,10 @@ Restated term by term:
 Randomness: upstream draws the samples from the global `np.random` stream, which nothing seeds and which the data
 loader's workers share, so no run of it can be reproduced.  Here the draws come from a `numpy.random.Generator` the
 caller owns (the trainer seeds it from --seed), in the order sel0, sel1, pos_sel.
+
+Kernels (`kernels=`, default ops.TRAIN_LOSS): "torch" is the body described above; "hip" draws the same samples from
+the same `rng` and hands them to csrc/loss.hip (autograd.HardestContrastiveLossFunction): the same quantities with every
+term in fp64 and every sum in a fixed order, forward and backward, without a host wait.
 """
 import numpy as np
 import torch
@@ -42,11 +46,17 @@ def _dev_index(a, device):
 
 
 def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_samples=2048, pos_thresh=0.1,
-                             neg_thresh=1.4, rng=None, sel0=None, sel1=None, pos_sel=None, return_indices=False):
+                             neg_thresh=1.4, rng=None, sel0=None, sel1=None, pos_sel=None, return_indices=False,
+                             kernels=None):
     """(pos_loss, neg_loss) of lib/trainer.py:440-493.  F0 [N0, C], F1 [N1, C] device float32 (with autograd);
     positive_pairs: [P, 2] integer tensor of (row of F0, row of F1).  Draws sel0 / sel1 / pos_sel from `rng` unless
     they are given (pos_sel=None with more than num_pos pairs and no rng is an error).  return_indices=True also
-    returns the hardest negatives as global rows: (D01ind into F1, D10ind into F0), int64 device tensors."""
+    returns the hardest negatives as global rows: (D01ind into F1, D10ind into F0), int64 device tensors.
+    kernels: "torch" or "hip" (csrc/loss.hip); None reads ops.TRAIN_LOSS."""
+    from .. import ops
+    kernels = ops.TRAIN_LOSS if kernels is None else kernels
+    if kernels not in ops.TRAIN_LOSS_CHOICES:
+        raise ops.ImfError(f"loss kernels {kernels!r}: one of {', '.join(ops.TRAIN_LOSS_CHOICES)}")
     dev = F0.device
     N0, N1 = F0.shape[0], F1.shape[0]
     P = positive_pairs.shape[0]
@@ -61,6 +71,12 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
         sel1 = d1 if sel1 is None else sel1
         pos_sel = dp if pos_sel is None else pos_sel
     pairs = positive_pairs.to(dev).long()
+    if kernels == "hip":
+        from ..autograd import HardestContrastiveLossFunction
+        out = HardestContrastiveLossFunction.apply(F0, F1, pairs.contiguous(),
+                                                   None if pos_sel is None else _dev_index(pos_sel, dev),
+                                                   _dev_index(sel0, dev), _dev_index(sel1, dev), pos_thresh, neg_thresh)
+        return out if return_indices else out[:2]
     sample = pairs if pos_sel is None else pairs[_dev_index(pos_sel, dev)]
     s0, s1 = _dev_index(sel0, dev), _dev_index(sel1, dev)
     subF0, subF1 = F0[s0], F1[s1]

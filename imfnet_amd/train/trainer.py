@@ -110,6 +110,9 @@ def make_parser():
     a("--norm_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="training-mode BatchNorm of the sparse path: torch ops, or the fused deterministic HIP kernels "
            "(fp64 statistics, ReLU and residual add folded in)")
+    a("--loss_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="the hardest-contrastive loss and its gradient: torch ops, or the deterministic HIP kernels "
+           "(fp64 terms in a fixed order, no host wait)")
     return p
 
 
@@ -164,6 +167,7 @@ class HardestContrastiveTrainer:
         self.device = torch.device(device)
         from .. import ops
         ops.set_train_norm(getattr(config, "norm_kernels", "torch"))
+        ops.set_train_loss(getattr(config, "loss_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)

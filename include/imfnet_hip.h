@@ -1003,6 +1003,48 @@ int imf_bn_train_backward(const float *dy, const float *x, const float *y, int r
                           const float *gamma, int64_t n, int c, float *dx, float *dgamma, float *dbeta, float *dresidual,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The hardest-contrastive loss of training (csrc/loss.hip) -----------------------------------------------------------
+ * Replaces: lib/trainer.py:440-493 `contrastive_hardest_negative_loss` and torch's autograd of it (row gathers whose
+ * backward is an atomic index_put, two sort-based isin calls, boolean-mask indexing that waits for the device).
+ * f0 [n0, c], f1 [n1, c] row-major fp32, 16-byte aligned; pairs int64 [n_pairs, 2] = (row of f0, row of f1); pos_sel int64
+ * [n_pos] rows of `pairs`, or NULL = every pair in order (then n_pos == n_pairs); sel0 [n_sel0] rows of f0, sel1 [n_sel1]
+ * rows of f1.  With (i_s, j_s) = pairs[pos_sel[s]], a_s = f0[i_s], b_s = f1[j_s]:
+ *   hard01[s] = sel1[argmin_k |a_s - f1[sel1[k]]|^2], hard10[s] = sel0[argmin_k |b_s - f0[sel0[k]]|^2]: imf_nn_search
+ *               itself (fp64 scores of the fp32 rows, a tie goes to the lowest k);
+ *   keep01[s] = 0 when (i_s, hard01[s]) is one of the n_pairs pairs, else 1; keep10[s] likewise for (hard10[s], j_s); exact,
+ *               on the key i + j * max(n0, n1) in an open-addressing set (integer compare-and-swap only);
+ *   loss[0]   = mean_s relu(|a_s - b_s|^2 - pos_thresh);
+ *   loss[1]   = (mean_{keep01} relu(neg_thresh - D01)^2 + mean_{keep10} relu(neg_thresh - D10)^2) / 2,
+ *               D01_s = sqrt(|a_s - f1[hard01_s]|^2 + 1e-7), D10_s = sqrt(|b_s - f0[hard10_s]|^2 + 1e-7);
+ *   meta      = (count of keep01, count of keep10, flags, 0); an empty keep set makes loss[1] NaN (the mean of nothing, as
+ *               torch), sends no gradient and raises flag bit 0 (keep01) or bit 1 (keep10).
+ * Every term is evaluated in fp64 from the fp32 rows, summed in fp64 in an order fixed by s alone, each output rounded
+ * once: |loss - exact| <= 2^-23 |exact|.
+ * backward: df0 [n0, c], df1 [n1, c] = the closed-form gradient of grad[0] * loss[0] + grad[1] * loss[1]; grad is fp32 [2]
+ * ON THE DEVICE.  Row i_s of f0 receives the positive term and the 01 term (as anchor), row hard10[s] the 10 term (as the
+ * negative; the minimum routes its gradient to the argmin only); f1 symmetrically.  Each element is one fp64 sum of its
+ * addends in an order that depends on the indices and c only, rounded once: |got - exact| <= 2^-23 * sum |addends|.  A row
+ * that no term touches is written as +0.0; the call writes all of df0 and df1 (the caller need not zero them).
+ * No floating-point atomics: two calls give the same bits.  Every call takes a stream and waits for nothing.
+ * IMF_EINVAL before any launch: c not in {16, 32, 64}, n_pos / n_pairs / n_sel0 / n_sel1 / n0 / n1 < 1, pos_sel NULL with
+ * n_pos != n_pairs, a null required pointer, a short or misaligned workspace.  IMF_EUNSUPPORTED: n_pos > 65536 (the entries
+ * are ranked by counting) or n_pairs > 2^26 (the key set).  Index VALUES are not validated.
+ * workspace: imf_hc_loss_workspace_bytes (0 for arguments the calls refuse), 16-byte aligned, for either call; nothing in
+ * it is carried from the forward to the backward. */
+size_t imf_hc_loss_workspace_bytes(int64_t n0, int64_t n1, int c, int64_t n_pairs, int64_t n_pos, int64_t n_sel0,
+                                   int64_t n_sel1);
+int imf_hc_loss_forward(const float *f0, int64_t n0, const float *f1, int64_t n1, int c, const int64_t *pairs,
+                        int64_t n_pairs, const int64_t *pos_sel /* or NULL */, int64_t n_pos, const int64_t *sel0,
+                        int64_t n_sel0, const int64_t *sel1, int64_t n_sel1, double pos_thresh, double neg_thresh,
+                        float *loss /* [2] */, int64_t *hard01 /* [n_pos] */, int64_t *hard10, uint8_t *keep01 /* [n_pos] */,
+                        uint8_t *keep10, int32_t *meta /* [4] */, void *workspace, size_t workspace_bytes, void *stream);
+int imf_hc_loss_backward(const float *f0, int64_t n0, const float *f1, int64_t n1, int c, const int64_t *pairs,
+                         int64_t n_pairs, const int64_t *pos_sel /* or NULL */, int64_t n_pos, const int64_t *sel0,
+                         int64_t n_sel0, const int64_t *sel1, int64_t n_sel1, double pos_thresh, double neg_thresh,
+                         const int64_t *hard01, const int64_t *hard10, const uint8_t *keep01, const uint8_t *keep10,
+                         const int32_t *meta, const float *grad /* [2], device */, float *df0, float *df1, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* ---- Descriptor Activation Mapping (csrc/dam.hip) ---------------------------------------------------------------------
  * Replaces: pytorch_dam/base_dam.py:120-173 + pytorch_dam/dam.py:15-21 -- 32 backward passes through the whole network per
  * target point, of which only final.kernel.grad is read -- by the closed form of that gradient, for T targets at once.

@@ -5,7 +5,7 @@ and imf_radius_pairs against scipy's cKDTree.
   geometry   random rotation, upload and first-occurrence voxelisation of every fragment of the batch
   pairs      radius_pairs (imf_radius_pairs) of every item at voxel x 1.5
   forward    the two batched training-mode forwards (forward_layers)
-  loss       hardest-contrastive loss (sampling, two nn_search calls, masks)
+  loss       hardest-contrastive loss (sampling, two nn_search calls, masks; --loss_kernels hip: csrc/loss.hip)
   backward   loss.backward()
   step       optimizer.step()
   iteration  the sum
@@ -15,7 +15,8 @@ radius_pairs at S25 (the fixture pair voxelised at 2.5 cm) and S50k (the fixture
 rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).query_ball_point(T src, r) on the host
 (one thread) for the same sets.
 
-Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--out FILE.json]
+Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
+       [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -85,6 +86,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--norm_kernels", default="torch", choices=("torch", "hip"))
+    ap.add_argument("--loss_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -96,7 +98,7 @@ def main():
         write_tree(root, clouds, images)
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
                             "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out"),
-                            "--norm_kernels", a.norm_kernels])
+                            "--norm_kernels", a.norm_kernels, "--loss_kernels", a.loss_kernels])
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -116,7 +118,7 @@ def main():
     for k in STAGES:
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
-    res.update(norm_kernels=a.norm_kernels, batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
+    res.update(norm_kernels=a.norm_kernels, loss_kernels=a.loss_kernels, batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
     ang = np.deg2rad(4.0)
     T[:3, :3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]]
