@@ -181,6 +181,12 @@ SIGNATURES = {
                                  _Z, _P]),
     "imf_hc_loss_backward": (_I, [_P, _L, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _D, _D, _P, _P, _P, _P, _P, _P, _P,
                                   _P, _P, _Z, _P]),
+    "imf_fusion_train_chunk_rows": (_I, []),
+    "imf_fusion_train_saved_bytes": (_Z, [_L, _I, _I]),
+    "imf_fusion_train_workspace_bytes": (_Z, [_L, _I, _I]),
+    "imf_fusion_train_forward": (_I, [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _P, _Z, _P, _P]),
+    "imf_fusion_train_backward": (_I, [_P, _P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _Z, _P, _P,
+                                       C.POINTER(C.c_void_p), _P, _P, _Z, _P]),
     "imf_dam_heat": (_I, [_P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "imf_ply_vertex_count": (_L, [C.c_char_p]),
     "imf_ply_read_points": (_L, [C.c_char_p, _P, _L]),

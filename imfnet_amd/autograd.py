@@ -20,6 +20,10 @@ backward; sparse.MinkowskiBatchNorm decides when it runs.
 hardest negatives and the closed-form gradient with respect to the two feature matrices, fp64 sums in a fixed order;
 train.loss.hardest_contrastive_loss decides when it runs.
 
+`AttentionFusionFunction` is the bottleneck point <-> image attention block (csrc/fusion_train.hip, ops.TRAIN_FUSION ==
+"hip"): every batch item in one forward and one backward call over a device-side partition of the rows;
+ResUNet2.transformer decides when it runs.
+
 Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
 two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
 range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
@@ -182,3 +186,31 @@ class HardestContrastiveLossFunction(torch.autograd.Function):
                                         meta, grad)
         return (df0.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
                 df1.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None, None, None, None, None, None, None)
+
+
+class AttentionFusionFunction(torch.autograd.Function):
+    """z = AttentionFusion(tokens, queries_encoder=x) of model/fusion.py (depth 0, one head) for every batch item at
+    once: x [n, 256] rows grouped by item, item_starts int32 [items + 1] on the device (ops.fusion_item_starts), tokens
+    [items, T, 128], then the block's 14 parameters in the order of ops.FUSION_TRAIN_PARAMS.  The backward computes only
+    the gradients autograd asks for; nothing on either way waits for the device."""
+
+    @staticmethod
+    def forward(ctx, x, item_starts, tokens, *params):
+        xc, tc = x.detach().contiguous(), tokens.detach().contiguous()
+        weights = [p.detach().contiguous() for p in params]
+        z, saved, _meta = ops.fusion_train_forward(xc, item_starts, tc, weights)
+        ctx.save_for_backward(xc, item_starts, tc, saved, *weights)
+        return z
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xc, item_starts, tc, saved, *weights = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        none = (None,) * (3 + len(weights))
+        if not any(need):
+            return none
+        if xc.shape[0] == 0:                         # no rows: the kernels launch nothing, every gradient is zero
+            return tuple(torch.zeros_like(t) if k else None for t, k in zip((xc, item_starts, tc, *weights), need))
+        dx, dtok, grads, _meta = ops.fusion_train_backward(grad_out.contiguous().float(), xc, item_starts, tc, weights,
+                                                           saved, need[0], need[2], need[3:])
+        return (dx, None, dtok, *grads)

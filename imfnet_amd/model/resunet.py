@@ -453,11 +453,37 @@ class ResUNet2(ME.MinkowskiNetwork):
         a, g = h.chunk(2, dim=-1)
         return F_.linear(a * F_.gelu(g), ff[2].weight, ff[2].bias) + x
 
+    def _fusion_kernels_apply(self, tokens, F):
+        """Whether the training kernels (csrc/fusion_train.hip) cover this call: the switch, training mode with autograd on, fp32
+        CUDA tensors and the one configuration they implement.  Everything else runs the torch body of `transformer`."""
+        if ops.TRAIN_FUSION != "hip" or not torch.is_grad_enabled() or not self.training:
+            return False
+        if not (F.is_cuda and tokens.is_cuda and F.dtype == torch.float32 and tokens.dtype == torch.float32 and F.dim() == 2):
+            return False
+        af = self.attention_fusion
+        if len(af.layers) != 0 or af.cross_attend_blocks[0].fn.heads != 1:
+            return False
+        if not 1 <= tokens.shape[1] <= ops.FUSION_TRAIN_MAX_TOKENS:
+            return False
+        latent, context, _, _ = ops.FUSION_TRAIN_DIMS
+        if F.shape[1] != latent or tokens.shape[2] != context:
+            return False
+        sd = dict(af.named_parameters())
+        return all(name in sd and tuple(sd[name].shape) == shape and sd[name].is_cuda and sd[name].dtype == torch.float32
+                   for name, shape in ops.FUSION_TRAIN_PARAMS) and len(sd) == len(ops.FUSION_TRAIN_PARAMS)
+
     def transformer(self, images, F, xyz):
         """Per batch item: the item's stride-8 rows attend over that item's image tokens
         (resunet.py:237-273).  Rows are grouped by batch index.  With one image there is no
         device->host traffic (the reference syncs three times here)."""
         tokens = images.flatten(2).transpose(1, 2)                    # [B, H*W, C]  (:257-261)
+        if self._fusion_kernels_apply(tokens, F):
+            # ops.TRAIN_FUSION == "hip": every item in one op over a device-side partition of the rows (a searchsorted
+            # over the batch column), forward and backward in csrc/fusion_train.hip -- no host wait
+            from ..autograd import AttentionFusionFunction
+            sd = dict(self.attention_fusion.named_parameters())
+            starts = ops.fusion_item_starts(xyz[:, 0], images.shape[0])
+            return AttentionFusionFunction.apply(F, starts, tokens, *[sd[name] for name, _ in ops.FUSION_TRAIN_PARAMS])
         if images.shape[0] == 1:
             return self.attention_fusion(tokens, queries_encoder=F.unsqueeze(0))[0]
         counts = torch.bincount(xyz[:, 0].long(), minlength=images.shape[0]).cpu().tolist()

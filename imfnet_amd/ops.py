@@ -860,6 +860,130 @@ def hc_loss_backward(f0, f1, pairs, pos_sel, sel0, sel1, pos_thresh, neg_thresh,
     return df0, df1
 
 
+# The bottleneck attention-fusion block of training (env IMF_TRAIN_FUSION; python -m imfnet_amd.train --fusion_kernels):
+#   "torch" (default) = model/fusion.py's torch ops, one batch item at a time, differentiated by torch's autograd;
+#   "hip"             = csrc/fusion_train.hip through autograd.AttentionFusionFunction: all items in one call, fp32 MFMA
+#                       products, sums over rows in a fixed chunk order, forward and backward, no floating-point
+#                       atomics, no host wait, bit-reproducible.  Used only under autograd on fp32 GPU tensors of the one
+#                       configuration IMFNet uses; every other call runs the torch ops whatever the switch.
+TRAIN_FUSION_CHOICES = ("torch", "hip")
+TRAIN_FUSION = os.environ.get("IMF_TRAIN_FUSION", "torch")
+if TRAIN_FUSION not in TRAIN_FUSION_CHOICES:
+    raise ImfError(f"IMF_TRAIN_FUSION={TRAIN_FUSION!r}: one of {', '.join(TRAIN_FUSION_CHOICES)}")
+
+
+def set_train_fusion(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_FUSION
+    if name not in TRAIN_FUSION_CHOICES:
+        raise ImfError(f"fusion kernels {name!r}: one of {', '.join(TRAIN_FUSION_CHOICES)}")
+    prev, TRAIN_FUSION = TRAIN_FUSION, name
+    return prev
+
+
+FUSION_TRAIN_DIMS = (256, 128, 128, 1024)         # latent, context, inner, GEGLU hidden
+FUSION_TRAIN_MAX_TOKENS = 320
+FUSION_TRAIN_FLAG_STARTS = 1                      # IMF_FT_FLAG_STARTS of the meta word
+# The block's 14 parameters in the order of the C ABI's IMF_FT_* indices: (name below AttentionFusion, shape)
+FUSION_TRAIN_PARAMS = (
+    ("cross_attend_blocks.0.norm.weight", (256,)), ("cross_attend_blocks.0.norm.bias", (256,)),
+    ("cross_attend_blocks.0.norm_context.weight", (128,)), ("cross_attend_blocks.0.norm_context.bias", (128,)),
+    ("cross_attend_blocks.0.fn.to_q.weight", (128, 256)), ("cross_attend_blocks.0.fn.to_kv.weight", (256, 128)),
+    ("cross_attend_blocks.0.fn.to_out.weight", (256, 128)), ("cross_attend_blocks.0.fn.to_out.bias", (256,)),
+    ("cross_attend_blocks.1.norm.weight", (256,)), ("cross_attend_blocks.1.norm.bias", (256,)),
+    ("cross_attend_blocks.1.fn.net.0.weight", (2048, 256)), ("cross_attend_blocks.1.fn.net.0.bias", (2048,)),
+    ("cross_attend_blocks.1.fn.net.2.weight", (256, 1024)), ("cross_attend_blocks.1.fn.net.2.bias", (256,)),
+)
+
+
+def fusion_train_chunk_rows():
+    return _lib.lib().imf_fusion_train_chunk_rows()
+
+
+def fusion_item_starts(batch_column, n_items):
+    """int32 [n_items + 1] row starts of the items from the (ascending) batch column of the rows' coordinates, on the
+    device: a searchsorted, no host wait."""
+    col = batch_column.contiguous()
+    edges = torch.arange(n_items + 1, dtype=col.dtype, device=col.device)
+    return torch.searchsorted(col, edges).to(torch.int32)
+
+
+def _fusion_train_args(x, starts, tokens, weights):
+    _req(x, torch.float32, "x", 2)
+    _req(tokens, torch.float32, "tokens", 3)
+    _req(starts, torch.int32, "item_starts", 1)
+    n, (n_items, T, ctx) = x.shape[0], tokens.shape
+    latent, context, _, _ = FUSION_TRAIN_DIMS
+    if x.shape[1] != latent or ctx != context:
+        raise ImfError(f"x must be [n, {latent}] and tokens [items, T, {context}], got {tuple(x.shape)} and {tuple(tokens.shape)}")
+    if not 1 <= T <= FUSION_TRAIN_MAX_TOKENS or n_items < 1:
+        raise ImfError(f"tokens [items >= 1, 1 <= T <= {FUSION_TRAIN_MAX_TOKENS}, {context}], got {tuple(tokens.shape)}")
+    if starts.shape[0] != n_items + 1:
+        raise ImfError(f"item_starts must be [{n_items + 1}], got {tuple(starts.shape)}")
+    if len(weights) != len(FUSION_TRAIN_PARAMS):
+        raise ImfError(f"{len(FUSION_TRAIN_PARAMS)} weights in the order of ops.FUSION_TRAIN_PARAMS, got {len(weights)}")
+    for t, (name, shape) in zip(weights, FUSION_TRAIN_PARAMS):
+        if tuple(_req(t, torch.float32, name).shape) != shape:
+            raise ImfError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    for name, t in (("tokens", tokens), ("item_starts", starts)) + tuple(zip((p[0] for p in FUSION_TRAIN_PARAMS), weights)):
+        if t.device != x.device:
+            raise ImfError(f"{name} is on {t.device}, x on {x.device}")
+    wptr = (C.c_void_p * len(weights))(*[t.data_ptr() for t in weights])
+    return n, n_items, T, wptr
+
+
+def fusion_train_forward(x, item_starts, tokens, weights, z=None):
+    """imf_fusion_train_forward: (z [n, 256], saved fp32 buffer, meta int32 [1]).  x [n, 256], item_starts int32
+    [items + 1] on the device (fusion_item_starts), tokens [items, T, 128], weights: the 14 parameters in the order of
+    FUSION_TRAIN_PARAMS.  meta[0] & FUSION_TRAIN_FLAG_STARTS: the starts were no partition of the rows; nothing here
+    waits for it."""
+    n, n_items, T, wptr = _fusion_train_args(x, item_starts, tokens, weights)
+    L = _lib.lib()
+    if z is None:
+        z = torch.empty_like(x)
+    elif tuple(_req(z, torch.float32, "z", 2).shape) != tuple(x.shape):
+        raise ImfError(f"z must be {tuple(x.shape)}, got {tuple(z.shape)}")
+    nbytes = L.imf_fusion_train_saved_bytes(n, n_items, T)
+    saved = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+    meta = torch.zeros(1, dtype=torch.int32, device=x.device)
+    check(L.imf_fusion_train_forward(x.data_ptr(), n, item_starts.data_ptr(), n_items, tokens.data_ptr(), T,
+                                     *FUSION_TRAIN_DIMS, wptr, z.data_ptr(), saved.data_ptr(), nbytes, meta.data_ptr(),
+                                     _stream()), "imf_fusion_train_forward")
+    return z, saved, meta
+
+
+def fusion_train_backward(dz, x, item_starts, tokens, weights, saved, want_dx=True, want_dtokens=True, want=None,
+                          outputs=None):
+    """imf_fusion_train_backward: (dx, dtokens, [14 parameter gradients], meta); None for what is not wanted (`want`: 14
+    booleans, default all).  `outputs` = (dx, dtokens, [14]) may hand in the tensors to write (None entries: not wanted)."""
+    n, n_items, T, wptr = _fusion_train_args(x, item_starts, tokens, weights)
+    if tuple(_req(dz, torch.float32, "dz", 2).shape) != tuple(x.shape) or dz.device != x.device:
+        raise ImfError(f"dz must be {tuple(x.shape)} on {x.device}")
+    L = _lib.lib()
+    sbytes = L.imf_fusion_train_saved_bytes(n, n_items, T)
+    if _req(saved, torch.float32, "saved", 1).shape[0] * 4 < sbytes or saved.device != x.device:
+        raise ImfError(f"saved must hold {sbytes} bytes on {x.device}")
+    if outputs is None:
+        want = [True] * len(weights) if want is None else list(want)
+        dx = torch.empty_like(x) if want_dx else None
+        dtok = torch.empty_like(tokens) if want_dtokens else None
+        grads = [torch.empty_like(t) if k else None for t, k in zip(weights, want)]
+    else:
+        dx, dtok, grads = outputs
+        for name, t, ref in [("dx", dx, x), ("dtokens", dtok, tokens)] + [(p[0], g, t) for p, g, t in
+                                                                         zip(FUSION_TRAIN_PARAMS, grads, weights)]:
+            if t is not None and (tuple(_req(t, torch.float32, name).shape) != tuple(ref.shape) or t.device != x.device):
+                raise ImfError(f"gradient of {name} must be {tuple(ref.shape)} on {x.device}")
+    gptr = (C.c_void_p * len(grads))(*[_ptr(t) for t in grads])
+    nbytes = L.imf_fusion_train_workspace_bytes(n, n_items, T)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+    meta = torch.zeros(1, dtype=torch.int32, device=x.device)
+    check(L.imf_fusion_train_backward(dz.data_ptr(), x.data_ptr(), n, item_starts.data_ptr(), n_items, tokens.data_ptr(),
+                                      T, *FUSION_TRAIN_DIMS, wptr, saved.data_ptr(), sbytes, _ptr(dx), _ptr(dtok), gptr,
+                                      meta.data_ptr(), ws.data_ptr(), nbytes, _stream()), "imf_fusion_train_backward")
+    return dx, dtok, grads, meta
+
+
 def dam_heat(out_prenorm, hidden, targets, accumulate=True, n_dev=None, heat=None):
     """imf_dam_heat (csrc/dam.hip): Descriptor Activation Mapping of T target rows at once.  out_prenorm [N, 32] = the
     output of `final` before normalisation, hidden [N, c_hid] = its input, targets int32 [T] on the device.  Returns

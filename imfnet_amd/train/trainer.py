@@ -113,6 +113,9 @@ def make_parser():
     a("--loss_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="the hardest-contrastive loss and its gradient: torch ops, or the deterministic HIP kernels "
            "(fp64 terms in a fixed order, no host wait)")
+    a("--fusion_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="the bottleneck point <-> image attention block and its gradients: torch ops per batch item, or the "
+           "deterministic HIP kernels (all items in one call, fixed summation order, no host wait)")
     return p
 
 
@@ -168,6 +171,7 @@ class HardestContrastiveTrainer:
         from .. import ops
         ops.set_train_norm(getattr(config, "norm_kernels", "torch"))
         ops.set_train_loss(getattr(config, "loss_kernels", "torch"))
+        ops.set_train_fusion(getattr(config, "fusion_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)

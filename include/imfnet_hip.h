@@ -1045,6 +1045,58 @@ int imf_hc_loss_backward(const float *f0, int64_t n0, const float *f1, int64_t n
                          const int32_t *meta, const float *grad /* [2], device */, float *df0, float *df1, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- The attention-fusion block in training (csrc/fusion_train.hip) ---------------------------------------------------
+ * Replaces: model/attention_fusion.py:132-154 (depth 0, one head, no mask) under autograd, and the host loop over batch
+ * items around it (model/resunet.py:237-273).  One configuration: latent 256, context 128, inner 128, GEGLU hidden 1024
+ * (passed explicitly; anything else is IMF_EINVAL), 1 <= n_tokens <= 320.
+ *   x [n, 256] row-major fp32, the rows of item b are [item_starts[b], item_starts[b + 1]);  item_starts int32
+ *   [n_items + 1] ON THE DEVICE, ascending, item_starts[0] = 0, item_starts[n_items] = n, an empty item is legal;
+ *   tokens [n_items, n_tokens, 128];  weights: IMF_FT_NPARAM device pointers in the order of the IMF_FT_* indices, each
+ *   in its parameter's own row-major [out, in] layout (nothing is packed);  z [n, 256].
+ *     c = LNc(tok_b), (k, v) = c Wkv^T;  q = LN1(x) Wq^T;  p = softmax(q k^T * 128^-1/2) over the item's tokens;
+ *     y = (p v) Wo^T + bo + x;  h = LN2(y) W1^T + b1 = (a, g);  z = (a * gelu_erf(g)) W2^T + b2 + y.
+ * forward: writes z and, into `saved` (imf_fusion_train_saved_bytes), what the backward reads again: the LayerNorm
+ *   statistics (mean, rstd per row), LN1(x), q, p, p v, y, LN2(y), h, the GEGLU output, LNc(tok) and (k, v).
+ * backward: dz [n, 256] -> dx [n, 256], dtokens [n_items, n_tokens, 128] and grads[IMF_FT_*] in the parameters' layouts.
+ *   dx, dtokens and every grads[i] may be NULL: that gradient, and whatever only it needs, is not computed; the bits of
+ *   the others do not change.  Every element of every non-NULL output is written (+0.0 in dtokens of an item without rows).
+ * fp32 throughout.  Products run on the fp32 MFMA, K ascending; LayerNorm and softmax rows are reduced by fixed xor
+ * butterflies; every sum over rows (the 14 parameter gradients, dk / dv per item) is cut into chunks of
+ * imf_fusion_train_chunk_rows() rows (counted from the range's first row), chunk partials added in chunk order in fp64
+ * and rounded once.  No floating-point atomics: two calls give the same bits, and a row of a batched forward equals that
+ * row of its item run alone.  Rows and tokens of padding contribute exactly nothing.
+ * meta: one int32 on the device, set to 0 by each call; IMF_FT_FLAG_STARTS is raised when an item's starts are not
+ *   0 <= s0 <= s1 <= n or the partition does not begin at 0 / end at n: that item is skipped and nothing outside the
+ *   outputs, `saved` and the workspace is ever written.  Neither call copies anything to the host or waits.
+ * n == 0 launches nothing and returns IMF_OK (no pointer is looked at, no output written: the gradients of a batch without
+ *   rows are the caller's zeros).  IMF_EINVAL before any device call: other dims, n_tokens outside 1 .. 320,
+ *   n < 0 or > 2^22, n_items < 1, a null required pointer, a short saved buffer or workspace, a pointer that is not
+ *   16-byte aligned.  workspace (backward only): imf_fusion_train_workspace_bytes, 16-byte aligned. */
+enum {
+  IMF_FT_LN1_G = 0, IMF_FT_LN1_B,      /* cross_attend_blocks.0.norm.{weight,bias}          [256] */
+  IMF_FT_LNC_G, IMF_FT_LNC_B,          /* cross_attend_blocks.0.norm_context.{weight,bias}  [128] */
+  IMF_FT_WQ,                           /* cross_attend_blocks.0.fn.to_q.weight              [128, 256] */
+  IMF_FT_WKV,                          /* cross_attend_blocks.0.fn.to_kv.weight             [256, 128] */
+  IMF_FT_WO, IMF_FT_BO,                /* cross_attend_blocks.0.fn.to_out.{weight,bias}     [256, 128], [256] */
+  IMF_FT_LN2_G, IMF_FT_LN2_B,          /* cross_attend_blocks.1.norm.{weight,bias}          [256] */
+  IMF_FT_W1, IMF_FT_B1,                /* cross_attend_blocks.1.fn.net.0.{weight,bias}      [2048, 256], [2048] */
+  IMF_FT_W2, IMF_FT_B2,                /* cross_attend_blocks.1.fn.net.2.{weight,bias}      [256, 1024], [256] */
+  IMF_FT_NPARAM
+};
+#define IMF_FT_FLAG_STARTS 1
+int imf_fusion_train_chunk_rows(void);
+size_t imf_fusion_train_saved_bytes(int64_t n, int n_items, int n_tokens);
+size_t imf_fusion_train_workspace_bytes(int64_t n, int n_items, int n_tokens);
+int imf_fusion_train_forward(const float *x, int64_t n, const int32_t *item_starts, int n_items, const float *tokens,
+                             int n_tokens, int latent_dim, int context_dim, int inner_dim, int hidden_dim,
+                             const float *const *weights /* host array [IMF_FT_NPARAM] */, float *z, float *saved,
+                             size_t saved_bytes, int32_t *meta, void *stream);
+int imf_fusion_train_backward(const float *dz, const float *x, int64_t n, const int32_t *item_starts, int n_items,
+                              const float *tokens, int n_tokens, int latent_dim, int context_dim, int inner_dim,
+                              int hidden_dim, const float *const *weights, const float *saved, size_t saved_bytes, float *dx,
+                              float *dtokens, float *const *grads /* host array [IMF_FT_NPARAM], entries may be NULL */,
+                              int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Descriptor Activation Mapping (csrc/dam.hip) ---------------------------------------------------------------------
  * Replaces: pytorch_dam/base_dam.py:120-173 + pytorch_dam/dam.py:15-21 -- 32 backward passes through the whole network per
  * target point, of which only final.kernel.grad is read -- by the closed form of that gradient, for T targets at once.

@@ -4,7 +4,7 @@ and imf_radius_pairs against scipy's cKDTree.
   decode     host decode of the batch's PLY files and images (sequential here; the trainer overlaps it on threads)
   geometry   random rotation, upload and first-occurrence voxelisation of every fragment of the batch
   pairs      radius_pairs (imf_radius_pairs) of every item at voxel x 1.5
-  forward    the two batched training-mode forwards (forward_layers)
+  forward    the two batched training-mode forwards (forward_layers; --fusion_kernels hip: csrc/fusion_train.hip)
   loss       hardest-contrastive loss (sampling, two nn_search calls, masks; --loss_kernels hip: csrc/loss.hip)
   backward   loss.backward()
   step       optimizer.step()
@@ -16,7 +16,7 @@ rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).quer
 (one thread) for the same sets.
 
 Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
-       [--out FILE.json]
+       [--fusion_kernels torch|hip] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -87,6 +87,7 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--norm_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--loss_kernels", default="torch", choices=("torch", "hip"))
+    ap.add_argument("--fusion_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -98,7 +99,8 @@ def main():
         write_tree(root, clouds, images)
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
                             "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out"),
-                            "--norm_kernels", a.norm_kernels, "--loss_kernels", a.loss_kernels])
+                            "--norm_kernels", a.norm_kernels, "--loss_kernels", a.loss_kernels,
+                            "--fusion_kernels", a.fusion_kernels])
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -118,7 +120,8 @@ def main():
     for k in STAGES:
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
-    res.update(norm_kernels=a.norm_kernels, loss_kernels=a.loss_kernels, batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
+    res.update(norm_kernels=a.norm_kernels, loss_kernels=a.loss_kernels, fusion_kernels=a.fusion_kernels,
+               batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
     ang = np.deg2rad(4.0)
     T[:3, :3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]]
