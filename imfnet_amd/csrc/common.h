@@ -103,6 +103,18 @@ __device__ __forceinline__ uint32_t hash_insert_key(uint64_t *keys, uint32_t cap
   }
 }
 
+// Membership in a key-only table: the probe sequence of hash_insert_key.
+__device__ __forceinline__ bool hash_contains_key(const uint64_t *__restrict__ keys, uint32_t capmask, uint64_t key) {
+  uint32_t s = hash64(key) & capmask;
+  while (true) {
+    const uint64_t k = keys[s];
+    if (k == key) return true;
+    if (k == kEmptyKey) return false;
+    s = (s + 1) & capmask;
+  }
+}
+
+// hash_insert, hash_find and hash_find_slot walk ONE probe sequence (hash_slot, then hash_step): change them together.
 // One 16-byte load per probe: key and row of a slot arrive together (a hit costs no second random line).
 __device__ __forceinline__ int hash_find(const imf_slot *__restrict__ tab, uint32_t capmask, uint64_t key, int shift) {
   uint32_t s = hash_slot(key, shift, capmask);
@@ -117,6 +129,35 @@ __device__ __forceinline__ int hash_find(const imf_slot *__restrict__ tab, uint3
   }
 }
 
+// The same walk, returning the slot that holds `key` (or -1) instead of its row: for tables whose slots index side arrays.
+__device__ __forceinline__ int hash_find_slot(const imf_slot *__restrict__ tab, uint32_t capmask, uint64_t key, int shift = 0) {
+  uint32_t s = hash_slot(key, shift, capmask);
+  uint32_t step = 0;
+  while (true) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(tab + s);
+    const uint64_t k = ((uint64_t)v.y << 32) | v.x;
+    if (k == key) return (int)s;
+    if (k == kEmptyKey) return -1;
+    if (!step) step = hash_step(key);
+    s = (s + step) & capmask;
+  }
+}
+
+// Sum / maximum over the 64 lanes of a wavefront, the result in every lane (butterfly, highest offset first).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// workspace carving on the host: sizes and addresses rounded up to 256 bytes; the 16-byte test of vector accesses
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace imf

@@ -173,7 +173,6 @@ k_bitgrid_fill(const int32_t *__restrict__ coords, long long n, uint32_t *grid, 
 
 constexpr int kBitsRows = 64;
 
-typedef _Float16 f16x8_b __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2_b __attribute__((ext_vector_type(2)));
 
 // conv1's weights as f16 B fragments: max |w| (block reduce over 256 threads) -> power-of-two scale -> THREE f16 parts per weight,
@@ -206,7 +205,7 @@ __device__ __forceinline__ float first_kernel_split(const float *__restrict__ w,
   }
   for (int i = tid; i < nkc * CBN * 64; i += 256) {
     const int ln = i & 63, cb = (i >> 6) % CBN, kc = i / (64 * CBN);
-    f16x8_b p0, p1, p2;
+    f16x8 p0, p1, p2;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const int k = 32 * kc + 16 * (t >> 2) + 4 * (ln >> 4) + (t & 3);
@@ -325,12 +324,12 @@ __device__ __forceinline__ void conv_first_bits_body(const int32_t *__restrict__
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       aw[j] = ((b8 >> (2 * j)) & 1u ? 0x3C00u : 0u) | ((b8 >> (2 * j + 1)) & 1u ? 0x3C000000u : 0u);   // f16 1.0 = 0x3C00
-    const f16x8_b a = __builtin_bit_cast(f16x8_b, make_uint4(aw[0], aw[1], aw[2], aw[3]));
+    const f16x8 a = __builtin_bit_cast(f16x8, make_uint4(aw[0], aw[1], aw[2], aw[3]));
 #pragma unroll
     for (int cb = 0; cb < CBN; ++cb) {
-      const f16x8_b b0 = __builtin_bit_cast(f16x8_b, W_l[((kc * CBN + cb) * kFirstParts + 0) * 64 + lane]);
-      const f16x8_b b1 = __builtin_bit_cast(f16x8_b, W_l[((kc * CBN + cb) * kFirstParts + 1) * 64 + lane]);
-      const f16x8_b b2 = __builtin_bit_cast(f16x8_b, W_l[((kc * CBN + cb) * kFirstParts + 2) * 64 + lane]);
+      const f16x8 b0 = __builtin_bit_cast(f16x8, W_l[((kc * CBN + cb) * kFirstParts + 0) * 64 + lane]);
+      const f16x8 b1 = __builtin_bit_cast(f16x8, W_l[((kc * CBN + cb) * kFirstParts + 1) * 64 + lane]);
+      const f16x8 b2 = __builtin_bit_cast(f16x8, W_l[((kc * CBN + cb) * kFirstParts + 2) * 64 + lane]);
       acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b2, acc[cb], 0, 0, 0);      // smallest parts first
       acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b1, acc[cb], 0, 0, 0);
       acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b0, acc[cb], 0, 0, 0);
@@ -530,7 +529,7 @@ int64_t imf_first_kernel_image_floats(int kvol, int cout) { return (int64_t)((kv
 int imf_pack_first_kernel(const float *w, int kvol, int cout, float *image, void *stream) {
   IMF_REQUIRE(w && image, "imf_pack_first_kernel: null pointer");
   IMF_REQUIRE((kvol == 27 || kvol == 125) && (cout == 32 || cout == 64), "imf_pack_first_kernel: kvol=%d cout=%d", kvol, cout);
-  IMF_REQUIRE(((uintptr_t)image & 15) == 0, "imf_pack_first_kernel: image must be 16-byte aligned");
+  IMF_REQUIRE(aligned16(image), "imf_pack_first_kernel: image must be 16-byte aligned");
   if (cout == 32) imf::k_pack_first_kernel<32><<<1, 256, 0, (hipStream_t)stream>>>(w, kvol, image);
   else            imf::k_pack_first_kernel<64><<<1, 256, 0, (hipStream_t)stream>>>(w, kvol, image);
   IMF_CHECK_LAUNCH("k_pack_first_kernel");

@@ -168,7 +168,7 @@ int imf_dam_heat(const float *out_prenorm, int64_t n, const int32_t *n_dev, cons
   if (T == 0) return IMF_OK;
   IMF_REQUIRE(targets && weights && minmax && flags && (n == 0 || (out_prenorm && hidden && heat)),
               "imf_dam_heat: null pointer");
-  IMF_REQUIRE(((uintptr_t)out_prenorm & 15) == 0, "imf_dam_heat: out_prenorm must be 16-byte aligned");
+  IMF_REQUIRE(aligned16(out_prenorm), "imf_dam_heat: out_prenorm must be 16-byte aligned");
   const int64_t row_blocks = div_up(n, kDamThreads), tiles = div_up(T, kDamTargetTile);
   IMF_REQUIRE(row_blocks <= 2147483647LL && tiles <= 65535, "imf_dam_heat: too many rows or targets");
   hipStream_t st = (hipStream_t)stream;

@@ -91,8 +91,6 @@ struct Layout {
   size_t buf_floats[NBUF], conv_ws_bytes, fusion_ws_bytes, float_bytes;
 };
 
-inline uintptr_t align256(uintptr_t a) { return (a + 255) & ~(uintptr_t)255; }
-
 // `capacity`: the fusion workspace of capacity mode.  The arenas may be null (the sizing entry points): the totals do not
 // depend on the addresses.
 Layout arena_layout(const Sizes &s, bool capacity, size_t bitgrid_words, const void *int_arena, const void *float_arena) {
@@ -753,7 +751,7 @@ int imf_fragment_forward(const imf_resunet_desc *net, const imf_image_desc *img,
   const Layout l = arena_layout(sizes_of(net, caps->rows), true, caps->bitgrid_words, fio->int_arena, fio->float_arena);
   IMF_REQUIRE(fio->int_arena_bytes >= l.int_bytes, "imf_fragment_forward: int arena %zu < %zu bytes", fio->int_arena_bytes,
               l.int_bytes);
-  IMF_REQUIRE(((uintptr_t)l.bitgrid & 15) == 0 && caps->bitgrid_words % 4 == 0, "imf_fragment_forward: bit grid must be 16-byte aligned, a multiple of 4 words");
+  IMF_REQUIRE(aligned16(l.bitgrid) && caps->bitgrid_words % 4 == 0, "imf_fragment_forward: bit grid must be 16-byte aligned, a multiple of 4 words");
   // ... and FILLED by the level-0 compaction kernel itself (the bounding box comes out of k_insert_points): no
   // k_bitgrid_fill launch between the pyramid and conv1
   pb.grid = l.bitgrid; pb.grid_words = caps->bitgrid_words; pb.grid_ksize = net->first_ksize;

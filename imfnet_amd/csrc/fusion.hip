@@ -144,15 +144,6 @@ __device__ __forceinline__ void frags_mma(f32x4 (&acc)[NC], const float *A, int 
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // LayerNorm of row `row` (256 wide, eps 1e-5, biased variance) from src to dst; one wave, 4 floats / lane
 __device__ __forceinline__ void layer_norm_row(const float *src, float *dst, const float *g, const float *b, int lane) {
   const float4 v = *reinterpret_cast<const float4 *>(src + 4 * lane);
@@ -412,7 +403,7 @@ int fusion_attention_dyn_fmt(const float *x, int64_t n_cap, const int32_t *n_dev
   IMF_REQUIRE(n_items >= 1 && n_items <= IMF_MAX_BATCH && n_cap > 0, "imf_fusion_attention_dyn: n_items=%d", n_items);
   IMF_REQUIRE(tokens_padded % 64 == 0 && tokens_padded <= kMaxTokP && n_tokens > 0 && n_tokens <= tokens_padded,
               "imf_fusion_attention_dyn: tokens=%d padded=%d", n_tokens, tokens_padded);
-  IMF_REQUIRE(workspace_bytes >= imf_fusion_workspace_bytes_cap(n_cap) && ((uintptr_t)workspace & 15) == 0,
+  IMF_REQUIRE(workspace_bytes >= imf_fusion_workspace_bytes_cap(n_cap) && aligned16(workspace),
               "imf_fusion_attention_dyn: needs %zu workspace bytes, 16-byte aligned", imf_fusion_workspace_bytes_cap(n_cap));
   FusionParams p;
   memset(&p, 0, sizeof(p));
@@ -482,7 +473,7 @@ int fusion_attention_batched_fmt(const float *x, int n_items, const int64_t *ite
     p.vp_b[b] = v_packed[b];
     n = n > item_row0[b] + item_rows[b] ? n : item_row0[b] + item_rows[b];
   }
-  IMF_REQUIRE(workspace && workspace_bytes >= imf_fusion_workspace_bytes(n) && ((uintptr_t)workspace & 15) == 0,
+  IMF_REQUIRE(workspace && workspace_bytes >= imf_fusion_workspace_bytes(n) && aligned16(workspace),
               "imf_fusion_attention: needs %zu workspace bytes, 16-byte aligned", imf_fusion_workspace_bytes(n));
   fill_params(p, x, w, n_tokens, tokens_padded, scale, (float *)workspace, n);
   p.n_items = n_items;

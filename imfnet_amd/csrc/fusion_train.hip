@@ -40,15 +40,6 @@ constexpr int kFtLdP = 320;      // row stride of the probabilities / score grad
 constexpr int kFtChunk = 256;    // rows per reduction chunk: part of the summation order, hence of the last bits
 constexpr int kFtThreads = 256;
 
-__device__ __forceinline__ float ft_wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float ft_wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // rows [r0, r1) of item b; false (and the flag) for a range that is not inside [0, n] or breaks the partition
 __device__ __forceinline__ bool ft_item_rows(const int32_t *__restrict__ starts, int b, int n_items, long long n,
                                              int32_t *meta, long long &r0, long long &r1) {
@@ -261,14 +252,14 @@ k_ft_ln(const float *__restrict__ x, long long rows, const float *__restrict__ g
     v[j] = x[row * W + PER * lane + j];
     s += v[j];
   }
-  const float mean = ft_wave_sum(s) * (1.f / W);
+  const float mean = wave_sum(s) * (1.f / W);
   float s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     v[j] -= mean;
     s2 = fmaf(v[j], v[j], s2);
   }
-  const float rstd = 1.f / sqrtf(ft_wave_sum(s2) * (1.f / W) + 1e-5f);
+  const float rstd = 1.f / sqrtf(wave_sum(s2) * (1.f / W) + 1e-5f);
 #pragma unroll
   for (int j = 0; j < PER; ++j)
     out[row * W + PER * lane + j] = fmaf(v[j] * rstd, gamma[PER * lane + j], beta[PER * lane + j]);
@@ -297,7 +288,7 @@ k_ft_ln_bwd(const float *__restrict__ dn, const float *__restrict__ x, const flo
     s1 += g[j];
     s2 = fmaf(g[j], xh[j], s2);
   }
-  const float m1 = ft_wave_sum(s1) * (1.f / W), m2 = ft_wave_sum(s2) * (1.f / W);
+  const float m1 = wave_sum(s1) * (1.f / W), m2 = wave_sum(s2) * (1.f / W);
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const long long at = row * W + PER * lane + j;
@@ -321,7 +312,7 @@ k_ft_softmax(float *__restrict__ P, long long n, int T) {
     v[i] = c < T ? srow[c] : -3.0e38f;
     m = fmaxf(m, v[i]);
   }
-  m = ft_wave_max(m);
+  m = wave_max(m);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
@@ -329,7 +320,7 @@ k_ft_softmax(float *__restrict__ P, long long n, int T) {
     v[i] = c < T ? expf(v[i] - m) : 0.f;
     s += v[i];
   }
-  s = ft_wave_sum(s);
+  s = wave_sum(s);
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int c = lane + 64 * i;
@@ -353,7 +344,7 @@ k_ft_softmax_bwd(const float *__restrict__ P, float *__restrict__ dP, long long 
     dv[i] = c < T ? drow[c] : 0.f;
     s = fmaf(pv[i], dv[i], s);
   }
-  s = ft_wave_sum(s);
+  s = wave_sum(s);
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int c = lane + 64 * i;
@@ -437,8 +428,6 @@ static bool ft_sizes_ok(int64_t n, int items, int T) {
   return n >= 0 && n <= (1 << 22) && items >= 1 && items <= 65535 && T >= 1 && T <= kFtMaxTok;
 }
 
-static inline bool ft_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 static FtRows ft_rows_args(const float *A, long long lda, const float *B, long long ldb, float *C, long long ldc, int N, int K,
                            long long rows) {
   FtRows p;
@@ -510,8 +499,8 @@ size_t imf_fusion_train_workspace_bytes(int64_t n, int n_items, int n_tokens) {
   for (int i = 0; i < IMF_FT_NPARAM; ++i) IMF_REQUIRE(weights[i], who ": null pointer (weights[%d])", i);                    \
   IMF_REQUIRE(saved_bytes >= imf_fusion_train_saved_bytes(n, n_items, n_tokens), who ": saved buffer too small (%zu bytes)", \
               imf_fusion_train_saved_bytes(n, n_items, n_tokens));                                                          \
-  IMF_REQUIRE(ft_aligned16(x) && ft_aligned16(tokens) && ft_aligned16(saved), who ": x, tokens and saved must be 16-byte aligned"); \
-  for (int i = 0; i < IMF_FT_NPARAM; ++i) IMF_REQUIRE(ft_aligned16(weights[i]), who ": weights[%d] must be 16-byte aligned", i)
+  IMF_REQUIRE(aligned16(x) && aligned16(tokens) && aligned16(saved), who ": x, tokens and saved must be 16-byte aligned"); \
+  for (int i = 0; i < IMF_FT_NPARAM; ++i) IMF_REQUIRE(aligned16(weights[i]), who ": weights[%d] must be 16-byte aligned", i)
 
 int imf_fusion_train_forward(const float *x, int64_t n, const int32_t *item_starts, int n_items, const float *tokens,
                              int n_tokens, int latent_dim, int context_dim, int inner_dim, int hidden_dim,
@@ -519,7 +508,7 @@ int imf_fusion_train_forward(const float *x, int64_t n, const int32_t *item_star
                              void *stream) {
   FT_REQUIRE_COMMON("imf_fusion_train_forward");
   IMF_REQUIRE(z, "imf_fusion_train_forward: null pointer (z)");
-  IMF_REQUIRE(ft_aligned16(z), "imf_fusion_train_forward: z must be 16-byte aligned");
+  IMF_REQUIRE(aligned16(z), "imf_fusion_train_forward: z must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int T = n_tokens, Tp = (int)div_up(T, 16) * 16;
   const long long BT = (long long)n_items * T;
@@ -581,7 +570,7 @@ int imf_fusion_train_backward(const float *dz, const float *x, int64_t n, const 
   IMF_REQUIRE(dz && grads && workspace, "imf_fusion_train_backward: null pointer");
   IMF_REQUIRE(workspace_bytes >= imf_fusion_train_workspace_bytes(n, n_items, n_tokens),
               "imf_fusion_train_backward: workspace too small (%zu bytes)", imf_fusion_train_workspace_bytes(n, n_items, n_tokens));
-  IMF_REQUIRE(ft_aligned16(dz) && ft_aligned16(workspace) && ft_aligned16(dx) && ft_aligned16(dtokens),
+  IMF_REQUIRE(aligned16(dz) && aligned16(workspace) && aligned16(dx) && aligned16(dtokens),
               "imf_fusion_train_backward: dz, dx, dtokens and workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int T = n_tokens, Tp = (int)div_up(T, 16) * 16;

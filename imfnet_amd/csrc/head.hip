@@ -21,30 +21,7 @@
 
 namespace imf {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-
 namespace {
-
-__device__ __forceinline__ void hd_split8(const float4 &x0, const float4 &x1, f16x8 &hi, f16x8 &lo) {
-#ifdef IMF_NOSPLIT_ABL   // timing experiment only (wrong results): what the conversion costs
-  hi = __builtin_bit_cast(f16x8, x0); lo = __builtin_bit_cast(f16x8, x1);
-  return;
-#endif
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const _Float16 h = (_Float16)v[t];
-    hi[t] = h;
-    lo[t] = (_Float16)(v[t] - (float)h);
-  }
-}
-
-// fragment reads behind __restrict__ parameters (alias-scope metadata): see spconv_g.hip
-__device__ __forceinline__ float4 hd_lds16(const float4 *__restrict__ src) { return *src; }
-__device__ __forceinline__ f16x8 hd_lds_f16x8(const float4 *__restrict__ src) {
-  return *reinterpret_cast<const f16x8 *>(src);
-}
 
 struct HeadParams {
   const float *in_a, *in_b;
@@ -160,17 +137,17 @@ k_pointwise_head(const HeadParams p) {
     for (int cc = 0; cc < NCC; ++cc) {
       f16x8 ah, al;
       if (PRE) {
-        ah = __builtin_bit_cast(f16x8, hd_lds16(&abuf[128 * cc + rd_slot]));
-        al = __builtin_bit_cast(f16x8, hd_lds16(&abuf[128 * cc + 64 + rd_slot]));
+        ah = __builtin_bit_cast(f16x8, lds_read16(&abuf[128 * cc + rd_slot]));
+        al = __builtin_bit_cast(f16x8, lds_read16(&abuf[128 * cc + 64 + rd_slot]));
       } else {
-        hd_split8(hd_lds16(&abuf[128 * cc + rd_slot]), hd_lds16(&abuf[128 * cc + 64 + rd_slot]), ah, al);
+        split8(lds_read16(&abuf[128 * cc + rd_slot]), lds_read16(&abuf[128 * cc + 64 + rd_slot]), ah, al);
       }
       const float4 *const wbuf = smem + cc * 512;
       f16x8 bh[4], bl[4];
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
-        bh[cb] = hd_lds_f16x8(&wbuf[(2 * cb) * 64 + lane]);
-        bl[cb] = hd_lds_f16x8(&wbuf[(2 * cb + 1) * 64 + lane]);
+        bh[cb] = lds_read_f16x8(&wbuf[(2 * cb) * 64 + lane]);
+        bl[cb] = lds_read_f16x8(&wbuf[(2 * cb + 1) * 64 + lane]);
       }
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[cb], acc[cb], 0, 0, 0);
@@ -202,7 +179,7 @@ k_pointwise_head(const HeadParams p) {
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
       f16x8 ah, al;
-      hd_split8(hd_lds16(&abuf[128 * cc + rd_slot]), hd_lds16(&abuf[128 * cc + 64 + rd_slot]), ah, al);
+      split8(lds_read16(&abuf[128 * cc + rd_slot]), lds_read16(&abuf[128 * cc + 64 + rd_slot]), ah, al);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) acc2[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, w2h[cc][cb], acc2[cb], 0, 0, 0);
 #pragma unroll
@@ -336,12 +313,12 @@ k_pointwise_head_b3(const HeadParams p) {
 #pragma unroll
     for (int cc = 0; cc < NCC; ++cc) {
       bf16x8 ap[3], bp[4][3];
-      split_b3(hd_lds16(&abuf[128 * cc + rd_slot]), hd_lds16(&abuf[128 * cc + 64 + rd_slot]), ap[0], ap[1], ap[2]);
+      split_b3(lds_read16(&abuf[128 * cc + rd_slot]), lds_read16(&abuf[128 * cc + 64 + rd_slot]), ap[0], ap[1], ap[2]);
       const float4 *const wbuf = smem + cc * 768;
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int h = 0; h < 3; ++h) bp[cb][h] = __builtin_bit_cast(bf16x8, hd_lds16(&wbuf[(3 * cb + h) * 64 + lane]));
+        for (int h = 0; h < 3; ++h) bp[cb][h] = __builtin_bit_cast(bf16x8, lds_read16(&wbuf[(3 * cb + h) * 64 + lane]));
 #define IMF_HB_TERM(I, J)                                                                              \
   _Pragma("unroll") for (int cb = 0; cb < 4; ++cb)                                                     \
       acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[I], bp[cb][J], acc[cb], 0, 0, 0);
@@ -369,7 +346,7 @@ k_pointwise_head_b3(const HeadParams p) {
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
       bf16x8 ap[3];
-      split_b3(hd_lds16(&abuf[128 * cc + rd_slot]), hd_lds16(&abuf[128 * cc + 64 + rd_slot]), ap[0], ap[1], ap[2]);
+      split_b3(lds_read16(&abuf[128 * cc + rd_slot]), lds_read16(&abuf[128 * cc + 64 + rd_slot]), ap[0], ap[1], ap[2]);
 #define IMF_HB_TERM(I, J)                                                                              \
   _Pragma("unroll") for (int cb = 0; cb < 2; ++cb)                                                     \
       acc2[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[I], w2[cc][cb][J], acc2[cb], 0, 0, 0);

@@ -84,20 +84,6 @@ __device__ __forceinline__ bool cell_of_point(V3 p, double inv_cell, int lim, in
   return true;
 }
 
-// the slot of a cell key, or -1 (same probe sequence as hash_insert)
-__device__ __forceinline__ int grid_find(const imf_slot *__restrict__ tab, uint32_t capmask, uint64_t key) {
-  uint32_t s = hash_slot(key, 0, capmask);
-  uint32_t step = 0;
-  while (true) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(tab + s);
-    const uint64_t k = ((uint64_t)v.y << 32) | v.x;
-    if (k == key) return (int)s;
-    if (k == kEmptyKey) return -1;
-    if (!step) step = hash_step(key);
-    s = (s + step) & capmask;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_grid_init(imf_slot *tab, int32_t *cnt, int64_t cap, int32_t *err) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) *err = 0;
@@ -170,7 +156,7 @@ __device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, doub
   for (int dz = -1; dz <= 1; ++dz)
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx) {
-        const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+        const int s = hash_find_slot(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
         if (s < 0) continue;
         const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
         const int r0 = (int)v.z, r1 = r0 + (int)v.w;
@@ -189,7 +175,7 @@ __device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, doub
 
 // fixed-order sum of a workgroup's per-thread values (xor butterfly per wavefront, then the 4 wavefronts in order)
 __device__ __forceinline__ double block_sum(double v, double *lds4) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) lds4[w] = v;
@@ -320,7 +306,7 @@ __global__ __launch_bounds__(256) void k_radius_count(Grid g, const double *__re
       for (int dz = -1; dz <= 1; ++dz)
         for (int dy = -1; dy <= 1; ++dy)
           for (int dx = -1; dx <= 1; ++dx) {
-            const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+            const int s = hash_find_slot(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
             if (s < 0) continue;
             const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
             for (int r = (int)v.z, r1 = (int)v.z + (int)v.w; r < r1; ++r) {
@@ -384,7 +370,7 @@ __global__ __launch_bounds__(256) void k_pairs_emit(Grid g, const double *__rest
     for (int dz = -1; dz <= 1; ++dz)
       for (int dy = -1; dy <= 1; ++dy)
         for (int dx = -1; dx <= 1; ++dx) {
-          const int s = grid_find(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+          const int s = hash_find_slot(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
           if (s < 0) continue;
           const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
           for (int r = (int)v.z, r1 = (int)v.z + (int)v.w; r < r1; ++r) {
@@ -408,16 +394,15 @@ struct GridLayout {
   int64_t cap;
   size_t tab, cnt, cell_of, xyz, idx, err, total;
 };
-inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 GridLayout grid_layout(int64_t n_dst) {
   GridLayout L;
   L.cap = imf_hash_capacity(n_dst);
   size_t p = 0;
-  L.tab = p;     p += al256((size_t)L.cap * sizeof(imf_slot));
-  L.cnt = p;     p += al256((size_t)L.cap * 4);
-  L.cell_of = p; p += al256((size_t)n_dst * 4);
-  L.xyz = p;     p += al256((size_t)n_dst * 24);
-  L.idx = p;     p += al256((size_t)n_dst * 4);
+  L.tab = p;     p += align256((size_t)L.cap * sizeof(imf_slot));
+  L.cnt = p;     p += align256((size_t)L.cap * 4);
+  L.cell_of = p; p += align256((size_t)n_dst * 4);
+  L.xyz = p;     p += align256((size_t)n_dst * 24);
+  L.idx = p;     p += align256((size_t)n_dst * 4);
   L.err = p;     p += 256;
   L.total = p;
   return L;
@@ -451,7 +436,7 @@ extern "C" {
 size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst) {
   if (n_src <= 0 || n_dst <= 0) return 0;
   const size_t nb = (size_t)div_up(n_src, kIcpThreads);
-  return grid_layout(n_dst).total + al256((size_t)n_src * 24) + al256(nb * kIcpRow * 8) + al256(sizeof(IcpState));
+  return grid_layout(n_dst).total + align256((size_t)n_src * 24) + align256(nb * kIcpRow * 8) + align256(sizeof(IcpState));
 }
 
 int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
@@ -473,8 +458,8 @@ int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, 
   if (rc) return rc;
   size_t p = grid_layout(n_dst).total;
   const int nb = (int)div_up(n_src, kIcpThreads);
-  double *cur = (double *)(ws + p);     p += al256((size_t)n_src * 24);
-  double *partial = (double *)(ws + p); p += al256((size_t)nb * kIcpRow * 8);
+  double *cur = (double *)(ws + p);     p += align256((size_t)n_src * 24);
+  double *partial = (double *)(ws + p); p += align256((size_t)nb * kIcpRow * 8);
   IcpState *state = (IcpState *)(ws + p);
   IcpInit init;
   for (int k = 0; k < 16; ++k) init.T[k] = init_host ? init_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
@@ -522,7 +507,7 @@ int imf_radius_count(const double *src, int64_t n_src, const double *dst, int64_
 // radius pairs: workspace = the grid, the per-point counts, the count pass's total
 size_t imf_radius_pairs_workspace_bytes(int64_t n_src, int64_t n_dst) {
   if (n_src <= 0 || n_dst <= 0) return 0;
-  return grid_layout(n_dst).total + al256((size_t)n_src * 4) + 256;
+  return grid_layout(n_dst).total + align256((size_t)n_src * 4) + 256;
 }
 
 int imf_radius_pairs(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host, double r,
@@ -552,7 +537,7 @@ int imf_radius_pairs(const double *src, int64_t n_src, const double *dst, int64_
   int rc = build_grid(dst, n_dst, r, ws, g, err, st);
   if (rc) return rc;
   size_t p = grid_layout(n_dst).total;
-  int32_t *cnt = (int32_t *)(ws + p);                              p += al256((size_t)n_src * 4);
+  int32_t *cnt = (int32_t *)(ws + p);                              p += align256((size_t)n_src * 4);
   unsigned long long *count_total = (unsigned long long *)(ws + p);
   IcpInit T;
   for (int k = 0; k < 16; ++k) T.T[k] = T_host ? T_host[k] : (k % 5 == 0 ? 1.0 : 0.0);

@@ -62,8 +62,6 @@ int32_t *place_table(Table &t, int32_t *p, int64_t n_out, int kvol) {
   return p;
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // Workspace layout: [tables: s1@4, s2 4->8, down 4->8, s1@8] [im2col] [stem out] [4 buffers @4] [4 buffers @8]
 // [LayerNorm'ed tokens] [kv] [split-K scratch]
 struct Plan {

@@ -41,16 +41,6 @@ __global__ __launch_bounds__(256) void k_kp_insert(const double *__restrict__ sa
   hash_insert_key(keys, capmask, k);
 }
 
-__device__ __forceinline__ bool set_contains(const uint64_t *__restrict__ keys, uint32_t capmask, uint64_t key) {
-  uint32_t s = hash64(key) & capmask;
-  while (true) {
-    const uint64_t k = keys[s];
-    if (k == key) return true;
-    if (k == kEmptyKey) return false;
-    s = (s + 1) & capmask;
-  }
-}
-
 __global__ __launch_bounds__(kKpBlock) void k_kp_probe(const double *__restrict__ coords, int64_t m,
                                                        double voxel, const uint64_t *__restrict__ keys,
                                                        uint32_t capmask, uint8_t *__restrict__ flags,
@@ -61,7 +51,7 @@ __global__ __launch_bounds__(kKpBlock) void k_kp_probe(const double *__restrict_
   if (i < m) {
     uint64_t k = fnv_key(coords + 3 * i, voxel);
     if (k == kEmptyKey) k = kEmptyKey - 1;
-    f = set_contains(keys, capmask, k) ? 1 : 0;
+    f = hash_contains_key(keys, capmask, k) ? 1 : 0;
     flags[i] = (uint8_t)f;
   }
   const unsigned long long bal = __ballot(f);

@@ -46,8 +46,6 @@ constexpr int64_t kHcMaxPairs = 1ll << 26;  // key set of at most 2^27 slots (1 
 constexpr double kHcEps = 1e-7;
 constexpr int kRankTile = 256;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 inline uint32_t hc_table_capacity(int64_t n_pairs) {
   uint32_t cap = 1024;
   while ((int64_t)cap < 2 * n_pairs) cap <<= 1;
@@ -86,16 +84,6 @@ HcLayout hc_layout(int64_t n_pos, int c, int64_t n_pairs, int64_t n_sel0, int64_
   L.coef = take((size_t)n_pos * 3 * 8);
   L.total = o;
   return L;
-}
-
-__device__ __forceinline__ bool hc_set_contains(const uint64_t *__restrict__ keys, uint32_t capmask, uint64_t key) {
-  uint32_t s = hash64(key) & capmask;
-  while (true) {
-    const uint64_t k = keys[s];
-    if (k == key) return true;
-    if (k == kEmptyKey) return false;
-    s = (s + 1) & capmask;
-  }
 }
 
 __device__ __forceinline__ int64_t hc_pair_row(const int64_t *__restrict__ pos_sel, int64_t s) {
@@ -188,8 +176,8 @@ __global__ __launch_bounds__(256) void k_hc_terms(const float *__restrict__ f0, 
   const int64_t h01 = sel1[nn01[s]], h10 = sel0[nn10[s]];
   const HcTerm t = hc_term<LP>(f0, f1, pairs, pos_sel, s, h01, h10, q);
   if (!live || q != 0) return;
-  const bool k01 = !hc_set_contains(table, capmask, (uint64_t)(t.i + h01 * hash_m));
-  const bool k10 = !hc_set_contains(table, capmask, (uint64_t)(h10 + t.j * hash_m));
+  const bool k01 = !hash_contains_key(table, capmask, (uint64_t)(t.i + h01 * hash_m));
+  const bool k10 = !hash_contains_key(table, capmask, (uint64_t)(h10 + t.j * hash_m));
   const double r01 = fmax(neg_thresh - t.d01, 0.0), r10 = fmax(neg_thresh - t.d10, 0.0);
   hard01[s] = h01;
   hard10[s] = h10;
@@ -388,7 +376,7 @@ int hc_check(const char *who, int64_t n0, int64_t n1, int c, int64_t n_pairs, in
   }
   const size_t need = hc_layout(n_pos, c, n_pairs, n_sel0, n_sel1).total;
   IMF_REQUIRE(workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-  IMF_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+  IMF_REQUIRE(aligned16(workspace), "%s: the workspace must be 16-byte aligned", who);
   return IMF_OK;
 }
 
@@ -417,7 +405,7 @@ int imf_hc_loss_forward(const float *f0, int64_t n0, const float *f1, int64_t n1
   const int rc = hc_check("imf_hc_loss_forward", n0, n1, c, n_pairs, n_pos, n_sel0, n_sel1, ptrs, pos_sel == nullptr,
                           workspace, workspace_bytes);
   if (rc != IMF_OK) return rc;
-  IMF_REQUIRE((((uintptr_t)f0 | (uintptr_t)f1) & 15) == 0, "imf_hc_loss_forward: f0 and f1 must be 16-byte aligned");
+  IMF_REQUIRE(aligned16(f0) && aligned16(f1), "imf_hc_loss_forward: f0 and f1 must be 16-byte aligned");
   const HcLayout L = hc_layout(n_pos, c, n_pairs, n_sel0, n_sel1);
   char *ws = (char *)workspace;
   float *pos0 = (float *)(ws + L.pos0), *pos1 = (float *)(ws + L.pos1);
@@ -467,7 +455,7 @@ int imf_hc_loss_backward(const float *f0, int64_t n0, const float *f1, int64_t n
   const int rc = hc_check("imf_hc_loss_backward", n0, n1, c, n_pairs, n_pos, n_sel0, n_sel1, ptrs, pos_sel == nullptr,
                           workspace, workspace_bytes);
   if (rc != IMF_OK) return rc;
-  IMF_REQUIRE((((uintptr_t)f0 | (uintptr_t)f1 | (uintptr_t)df0 | (uintptr_t)df1) & 15) == 0,
+  IMF_REQUIRE(aligned16(f0) && aligned16(f1) && aligned16(df0) && aligned16(df1),
               "imf_hc_loss_backward: f0, f1, df0 and df1 must be 16-byte aligned");
   const HcLayout L = hc_layout(n_pos, c, n_pairs, n_sel0, n_sel1);
   char *ws = (char *)workspace;

@@ -281,8 +281,6 @@ k_bn_bwd_dx(const float *__restrict__ dy, const float *__restrict__ x, const flo
   }
 }
 
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 static inline dim3 bn_grid(int64_t chunks, int c, int vec) {
   const int groups = c / vec;
   const int width = groups < kBnTileGroups ? groups : kBnTileGroups;

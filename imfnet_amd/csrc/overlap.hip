@@ -51,8 +51,6 @@ constexpr int kOvFlagRange = 1;                    // a point that is NaN or bey
 constexpr int kEmitBlock = 1024;                   // rows per block of the emit scan
 constexpr int64_t kOvMaxPoints = 1ll << 26;
 
-inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct OvLayout {
   int64_t cap;
   size_t tab, xyz, idx, cells, chunks, meta, total;
@@ -61,11 +59,11 @@ OvLayout ov_layout(int64_t n) {
   OvLayout L;
   L.cap = imf_hash_capacity(n);
   size_t p = 0;
-  L.tab = p;    p += al256((size_t)L.cap * sizeof(imf_slot));
-  L.xyz = p;    p += al256((size_t)n * 12);
-  L.idx = p;    p += al256((size_t)n * 4);
-  L.cells = p;  p += al256((size_t)n * 4);
-  L.chunks = p; p += al256((size_t)n * 8);
+  L.tab = p;    p += align256((size_t)L.cap * sizeof(imf_slot));
+  L.xyz = p;    p += align256((size_t)n * 12);
+  L.idx = p;    p += align256((size_t)n * 4);
+  L.cells = p;  p += align256((size_t)n * 4);
+  L.chunks = p; p += align256((size_t)n * 8);
   L.meta = p;   p += 256;
   L.total = p;
   return L;
@@ -75,20 +73,6 @@ __device__ __forceinline__ void cell_of_key(uint64_t k, int &x, int &y, int &z) 
   x = ((int)((k >> (2 * kCoordBits)) & 0x3FFFF) << 14) >> 14;     // sign-extend the 18-bit fields
   y = ((int)((k >> kCoordBits) & 0x3FFFF) << 14) >> 14;
   z = ((int)(k & 0x3FFFF) << 14) >> 14;
-}
-
-// the slot of a cell key, or -1 (the probe sequence of hash_insert)
-__device__ __forceinline__ int ov_find(const imf_slot *__restrict__ tab, uint32_t capmask, uint64_t key) {
-  uint32_t s = hash_slot(key, 0, capmask);
-  uint32_t step = 0;
-  while (true) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(tab + s);
-    const uint64_t k = ((uint64_t)v.y << 32) | v.x;
-    if (k == key) return (int)s;
-    if (k == kEmptyKey) return -1;
-    if (!step) step = hash_step(key);
-    s = (s + step) & capmask;
-  }
 }
 
 __global__ __launch_bounds__(256) void k_ov_init(imf_slot *tab, int64_t cap, int32_t *meta) {
@@ -187,7 +171,7 @@ __global__ __launch_bounds__(256) void k_ov_bound(const imf_overlap_index *__res
     bool hit = false;
     for (int dz = -1; dz <= 1 && !hit; ++dz)
       for (int dy = -1; dy <= 1 && !hit; ++dy)
-        for (int dx = -1; dx <= 1 && !hit; ++dx) hit = ov_find(P.table, capmask, pack_key(0, x + dx, y + dy, z + dz)) >= 0;
+        for (int dx = -1; dx <= 1 && !hit; ++dx) hit = hash_find_slot(P.table, capmask, pack_key(0, x + dx, y + dy, z + dz)) >= 0;
     if (hit) add = (unsigned long long)v.w;
   }
   for (int o = 32; o > 0; o >>= 1) add += __shfl_xor(add, o, 64);
@@ -212,7 +196,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_pair(imf_overlap_index P, imf
   if (t < 27) {
     int x, y, z;
     cell_of_key(((uint64_t)qc.y << 32) | qc.x, x, y, z);
-    const int s = ov_find(P.table, (uint32_t)(P.capacity - 1), pack_key(0, x + t % 3 - 1, y + (t / 3) % 3 - 1, z + t / 9 - 1));
+    const int s = hash_find_slot(P.table, (uint32_t)(P.capacity - 1), pack_key(0, x + t % 3 - 1, y + (t / 3) % 3 - 1, z + t / 9 - 1));
     int32_t row = 0, cnt = 0;
     if (s >= 0) {
       const uint4 v = *reinterpret_cast<const uint4 *>(P.table + s);
@@ -341,7 +325,7 @@ size_t imf_overlap_index_bytes(int64_t n) {
 
 size_t imf_overlap_index_workspace_bytes(int64_t n) {
   if (n <= 0 || n > kOvMaxPoints) return 0;
-  return al256((size_t)n * 4) + al256((size_t)imf_hash_capacity(n) * 4);
+  return align256((size_t)n * 4) + align256((size_t)imf_hash_capacity(n) * 4);
 }
 
 int imf_overlap_index_build(const float *points, int64_t n, double cell, void *storage, size_t storage_bytes,
@@ -367,7 +351,7 @@ int imf_overlap_index_build(const float *points, int64_t n, double cell, void *s
   index->meta = (int32_t *)(base + L.meta);
   index->n = n;
   index->cell = cell;
-  int32_t *cell_of = (int32_t *)ws, *cursor = (int32_t *)(ws + al256((size_t)n * 4));
+  int32_t *cell_of = (int32_t *)ws, *cursor = (int32_t *)(ws + align256((size_t)n * 4));
   const unsigned nb = (unsigned)div_up(n, 256);
   k_ov_init<<<(unsigned)div_up(L.cap, 256), 256, 0, st>>>(index->table, L.cap, index->meta);
   k_ov_insert<<<nb, 256, 0, st>>>(points, n, 1.0 / cell, index->table, (uint32_t)(L.cap - 1), cell_of, index->meta);
@@ -410,7 +394,7 @@ int imf_overlap_pair(const imf_overlap_index *p, const imf_overlap_index *q, flo
 
 size_t imf_overlap_emit_workspace_bytes(int64_t n_q) {
   if (n_q <= 0 || n_q > kOvMaxPoints) return 0;
-  return al256((size_t)div_up(n_q, kEmitBlock) * 4);
+  return align256((size_t)div_up(n_q, kEmitBlock) * 4);
 }
 
 int imf_overlap_emit(const int32_t *nn_idx, int64_t n_q, int64_t *pairs, int64_t *out_n, void *workspace,

@@ -224,8 +224,6 @@ __global__ __launch_bounds__(kRtThreads) void k_robust_transform(const double *_
   if (t == 16) out_meta[0] = sh.bad;
 }
 
-inline size_t rt_al256(size_t v) { return (v + 255) / 256 * 256; }
-
 const double kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 const int32_t kFlagged = 1;
 
@@ -238,7 +236,7 @@ extern "C" {
 
 size_t imf_robust_transform_workspace_bytes(int64_t n) {
   if (n <= (int64_t)kRtThreads * kRtRows) return 0;
-  return rt_al256((size_t)n * 24) + rt_al256((size_t)n * 8);
+  return align256((size_t)n * 24) + align256((size_t)n * 8);
 }
 
 int imf_robust_transform(const double *pts0, const double *pts1, const double *weight, int64_t n, double *out_T,
@@ -260,7 +258,7 @@ int imf_robust_transform(const double *pts0, const double *pts1, const double *w
     IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_robust_transform: workspace must be 256-byte aligned");
     IMF_REQUIRE(workspace_bytes >= need, "imf_robust_transform: workspace %zu < %zu", workspace_bytes, need);
     double *cur = (double *)workspace;
-    double *wgt = (double *)((char *)workspace + rt_al256((size_t)n * 24));
+    double *wgt = (double *)((char *)workspace + align256((size_t)n * 24));
     k_robust_transform<false><<<1, kRtThreads, 0, st>>>(pts0, pts1, weight, n, cur, wgt, out_T, out_meta);
   }
   IMF_CHECK_LAUNCH("imf_robust_transform");

@@ -47,35 +47,6 @@
 
 namespace imf {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-namespace {
-
-constexpr int kDummyJk = kKCache - 1;        // neighbour-table row that is always "no input"
-constexpr unsigned kNoRow = 0x00FFFFFFu;     // 24-bit row index whose byte offset falls outside the buffer window
-
-__device__ __forceinline__ void split8(const float4 &x0, const float4 &x1, f16x8 &hi, f16x8 &lo) {
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const _Float16 h = (_Float16)v[t];
-    hi[t] = h;
-    lo[t] = (_Float16)(v[t] - (float)h);
-  }
-}
-
-// LDS fragment reads behind __restrict__ parameters: after inlining they carry alias-scope metadata, and hipcc's
-// waitcnt pass then orders them only against LDS-DMA stores it can prove to alias (ours carry no scope info: none).
-// Without the metadata it puts `s_waitcnt vmcnt(0)` before every ds_read that follows a DMA issue -- the ordering is
-// ours to guarantee (counted waits + barriers in the loops below).
-__device__ __forceinline__ float4 lds_read16(const float4 *__restrict__ src) { return *src; }
-__device__ __forceinline__ f16x8 lds_read_f16x8(const float4 *__restrict__ src) {
-  return *reinterpret_cast<const f16x8 *>(src);
-}
-
-}  // namespace
-
 // NB = LDS buffers per workgroup = sub-stages in flight + 1.  NB 2 (four workgroups per CU at RB 1) for launches that
 // fill the chip several times over; NB 4 (two per CU, three sub-stages in flight) for launches whose few workgroups
 // cannot hide the ~2 k-cycle DMA latency behind each other (launch_spconv_g picks).

@@ -14,8 +14,6 @@
 
 namespace imf {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // Packed image (same size as the fp32 one: two halves per weight):
 //   [y][k][cc][q = 2 cb + h][lane][t],  ci = 32 cc + 16 (t>>2) + 4 (lane>>4) + (t&3),  co = y CW + 16 cb + (lane&15),
 //   (the contraction index of the MFMA is free to permute: lane group q holds channels 4q..4q+3 and 16+4q..16+4q+3 so that

@@ -1,10 +1,12 @@
-// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_g.hip, spconv_w.hip, conv_first.hip).
+// Pieces shared by the sparse-convolution kernels (spconv.hip, spconv_g.hip, spconv_w.hip, conv_first.hip, head.hip).
 #pragma once
 #include "common.h"
 
 namespace imf {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) void lds_void;   // destination of an LDS-DMA (raw_ptr_buffer_load_lds)
 
 // Arithmetic of the LDS-DMA convolution kernels' main loops (template argument AR of k_spconv_g / k_spconv_w).
 constexpr int kArF16x2 = 0;      // variant 6: fp32 rows split into f16 hi + lo in registers
@@ -261,7 +263,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams &p, const f32x4 (
 template <int CO_BLK>
 __device__ __forceinline__ void conv_epilogue_staged(const ConvParams &p, const f32x4 (&acc)[CO_BLK], float *stage, int tile,
                                                      int y, int wave, int lane, float unscale) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   constexpr int CW = 16 * CO_BLK, LD = CW + 4, PPR = CW / 8;   // pieces per row: 8 or 4
   const int r16 = lane & 15, q4 = lane >> 4;
 #pragma unroll
@@ -294,7 +295,7 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvParams &p, const 
     if (p.residual) {
       if (p.res_split) {
         const _Float16 *const src = reinterpret_cast<const _Float16 *>(p.residual) + split_index(orow, p.cout, col);
-        const h8 rh = *reinterpret_cast<const h8 *>(src), rl = *reinterpret_cast<const h8 *>(src + 32);
+        const f16x8 rh = *reinterpret_cast<const f16x8 *>(src), rl = *reinterpret_cast<const f16x8 *>(src + 32);
 #pragma unroll
         for (int t = 0; t < 8; ++t) x[t] += (float)rh[t] + (float)rl[t];
       } else {
@@ -310,15 +311,15 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvParams &p, const 
 #pragma unroll
     for (int t = 0; t < 8; ++t) bad |= out_of_f16_range(x[t]);
     if (p.out_split) {
-      h8 oh, ol;
+      f16x8 oh, ol;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         oh[t] = (_Float16)x[t];
         ol[t] = (_Float16)(x[t] - (float)oh[t]);
       }
       _Float16 *const dst = reinterpret_cast<_Float16 *>(p.out) + split_index(orow, p.cout, col);
-      *reinterpret_cast<h8 *>(dst) = oh;
-      *reinterpret_cast<h8 *>(dst + 32) = ol;
+      *reinterpret_cast<f16x8 *>(dst) = oh;
+      *reinterpret_cast<f16x8 *>(dst + 32) = ol;
     } else {
       *reinterpret_cast<float4 *>(p.out + orow * p.cout + col) = make_float4(x[0], x[1], x[2], x[3]);
       *reinterpret_cast<float4 *>(p.out + orow * p.cout + col + 16) = make_float4(x[4], x[5], x[6], x[7]);
@@ -370,6 +371,40 @@ __device__ __forceinline__ void fused_reduce_tile(const ConvParams &p, int S, lo
 
 constexpr int kKCache = 28;   // active offsets cached per workgroup (kvol <= 27 uses the pipelined kernels)
 constexpr int kSubTab = 27 * 8 + 8;   // variant 6: sub-stage table entries per workgroup; kvol * cin / 32 must stay below it
+
+// ---- Row staging of the LDS-DMA kernels (k_spconv_g, k_spconv_w, k_pointwise_head, k_pointwise_head_b3) ----
+constexpr int kDummyJk = kKCache - 1;        // neighbour-table row that is always "no input"
+constexpr unsigned kNoRow = 0x00FFFFFFu;     // 24-bit row index whose byte offset falls outside the buffer window
+
+// fp32 -> f16 hi + lo (variant 6): what lane (row, j) builds from pieces j and 4 + j of a 32-channel chunk
+__device__ __forceinline__ void split8(const float4 &x0, const float4 &x1, f16x8 &hi, f16x8 &lo) {
+#ifdef IMF_NOSPLIT_ABL   // timing experiment only (wrong results): what the conversion costs
+  hi = __builtin_bit_cast(f16x8, x0); lo = __builtin_bit_cast(f16x8, x1);
+  return;
+#endif
+  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const _Float16 h = (_Float16)v[t];
+    hi[t] = h;
+    lo[t] = (_Float16)(v[t] - (float)h);
+  }
+}
+
+// LDS fragment reads behind __restrict__ parameters: after inlining they carry alias-scope metadata, and hipcc's
+// waitcnt pass then orders them only against LDS-DMA stores it can prove to alias (ours carry no scope info: none).
+// Without the metadata it puts `s_waitcnt vmcnt(0)` before every ds_read that follows a DMA issue -- the ordering is
+// the kernel's to guarantee (counted waits + barriers in its loops).  Every read of a DMA-filled LDS region goes
+// through one of these.
+__device__ __forceinline__ float4 lds_read16(const float4 *__restrict__ src) { return *src; }
+__device__ __forceinline__ f16x8 lds_read_f16x8(const float4 *__restrict__ src) {
+  return *reinterpret_cast<const f16x8 *>(src);
+}
+__device__ __forceinline__ unsigned lds_read_u32(const unsigned *__restrict__ src) { return *src; }
+
+// The lane swizzle of the row image (writer byte 16 ((lane & 3) ^ f(lane >> 4)), reader slot 4 r16 + (q4 ^ f(r16 >> 2)),
+// f(x) = (4 - x) & 3; layout: head comment of spconv_g.hip) stays spelled out in each kernel: behind a function the index
+// arithmetic is simplified before it is inlined and every kernel's schedule moves (LAB_NOTES.md, "Shared device helpers").
 
 // spconv_g.hip: variants 6 / 3 / 0 with both operands staged by LDS-DMA; grid = (tiles, cout / (16 CB), split)
 void launch_spconv_g(const ConvParams &p, dim3 grid, int co_blk, hipStream_t st, int use = 0);

@@ -43,37 +43,6 @@
 
 namespace imf {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-namespace {
-
-constexpr int kDummyJkW = kKCache - 1;        // neighbour-table row that is always "no input"
-constexpr unsigned kNoRowW = 0x00FFFFFFu;     // 24-bit row index whose byte offset falls outside the buffer window
-
-__device__ __forceinline__ void w_split8(const float4 &x0, const float4 &x1, f16x8 &hi, f16x8 &lo) {
-#ifdef IMF_NOSPLIT_ABL   // timing experiment only (wrong results): what the conversion costs
-  hi = __builtin_bit_cast(f16x8, x0); lo = __builtin_bit_cast(f16x8, x1);
-  return;
-#endif
-  const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const _Float16 h = (_Float16)v[t];
-    hi[t] = h;
-    lo[t] = (_Float16)(v[t] - (float)h);
-  }
-}
-
-// fragment reads behind __restrict__ parameters (alias-scope metadata): see spconv_g.hip
-__device__ __forceinline__ float4 w_lds16(const float4 *__restrict__ src) { return *src; }
-__device__ __forceinline__ f16x8 w_lds_f16x8(const float4 *__restrict__ src) {
-  return *reinterpret_cast<const f16x8 *>(src);
-}
-__device__ __forceinline__ unsigned w_lds_u32(const unsigned *__restrict__ src) { return *src; }
-
-}  // namespace
-
 // AR (spconv_shared.h): the arithmetic of the main loop.
 //   kArF16x2      fp32 rows split into f16 hi + lo in registers, 3 x v_mfma_f32_16x16x32_f16 per 32 channels (variant 6)
 //   kArF16x2Pre   the same products; the input rows are split-f16 operand images (ConvParams::a_split) -- no conversion
@@ -190,7 +159,7 @@ k_spconv_w(const ConvParams p) {
       for (int i = 0; i < kPer; ++i) v[i] = row_of_slot(p, slot);
     }
     if (tid < kSubTab) {
-      unsigned e = (unsigned)kDummyJkW << 9;
+      unsigned e = (unsigned)kDummyJk << 9;
       if (tid < n_sub) {
         const int jk = tid / ncc, cc = tid - jk * ncc;
         const int ch0 = cc * 32;
@@ -203,8 +172,8 @@ k_spconv_w(const ConvParams p) {
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const int j = j0 + JSTEP * i;
-      if (j < nk) nbr_lds[j * IMF_TILE_ROWS + srow] = (v[i] >= 0 && in_unit) ? (unsigned)v[i] : kNoRowW;
-      else if (j == kDummyJkW) nbr_lds[j * IMF_TILE_ROWS + srow] = kNoRowW;
+      if (j < nk) nbr_lds[j * IMF_TILE_ROWS + srow] = (v[i] >= 0 && in_unit) ? (unsigned)v[i] : kNoRow;
+      else if (j == kDummyJk) nbr_lds[j * IMF_TILE_ROWS + srow] = kNoRow;
     }
   }
   __syncthreads();
@@ -236,7 +205,7 @@ k_spconv_w(const ConvParams p) {
 #define IMF_W_ROWS(dst, e)                                                                                         \
   {                                                                                                                \
     const unsigned *const base_ = nbr_lds + ((((unsigned)(e)) >> 9) & 31u) * IMF_TILE_ROWS + row_w;                \
-    _Pragma("unroll") for (int b_ = 0; b_ < RB; ++b_) (dst).r[b_] = w_lds_u32(base_ + 16 * b_);                    \
+    _Pragma("unroll") for (int b_ = 0; b_ < RB; ++b_) (dst).r[b_] = lds_read_u32(base_ + 16 * b_);                    \
   }
   // LDS-DMA of one sub-stage into the wavefront's region: 8 KiB of weights verbatim, 64 rows x 128 B as 8 images
 #define IMF_W_DMA(e, rows)                                                                                         \
@@ -288,7 +257,7 @@ k_spconv_w(const ConvParams p) {
   unsigned e_cur = 0, e_nxt = 0;
   Rows rows_nxt;
   if (t0 < t1) {
-    e_cur = (unsigned)__builtin_amdgcn_readfirstlane((int)w_lds_u32(&stab[t0]));
+    e_cur = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32(&stab[t0]));
     Rows rows0;
     IMF_W_ROWS(rows0, e_cur)
     if constexpr (AR == kArBf16x3) {
@@ -296,7 +265,7 @@ k_spconv_w(const ConvParams p) {
     } else {
       IMF_W_DMA(e_cur, rows0)
     }
-    e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)w_lds_u32(&stab[t0 + 1 < kSubTab ? t0 + 1 : kSubTab - 1]));
+    e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32(&stab[t0 + 1 < kSubTab ? t0 + 1 : kSubTab - 1]));
     IMF_W_ROWS(rows_nxt, e_nxt)
   }
   // A sub-stage of a wavefront is two segments, LOAD (wait for its DMAs, 16 fragment reads, issue the 16 DMA pieces of the
@@ -345,13 +314,13 @@ k_spconv_w(const ConvParams p) {
 #pragma unroll
       for (int b = 0; b < RB; ++b) {
         if (IMF_W_ABL & 256) { a0[b] = make_float4((float)t, 1.f, 2.f, (float)lane); a1[b] = a0[b]; continue; }
-        a0[b] = w_lds16(&areg[128 * b + rd_slot]);
-        a1[b] = w_lds16(&areg[128 * b + 64 + rd_slot]);
+        a0[b] = lds_read16(&areg[128 * b + rd_slot]);
+        a1[b] = lds_read16(&areg[128 * b + 64 + rd_slot]);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the row region is free
       if (!more) {
 #pragma unroll
-        for (int b = 0; b < RB; ++b) rows_nxt.r[b] = kNoRowW;
+        for (int b = 0; b < RB; ++b) rows_nxt.r[b] = kNoRow;
       }
       if (!(IMF_W_ABL & 32)) IMF_W_DMA_ROWS(e_nxt, rows_nxt)      // rows of t + 1: a whole sub-stage to land
       __builtin_amdgcn_sched_barrier(0);                          // (the scheduler otherwise sinks the requests below ~40 MFMAs)
@@ -380,7 +349,7 @@ k_spconv_w(const ConvParams p) {
       __builtin_amdgcn_sched_barrier(0);
       if (!(IMF_W_ABL & 16)) IMF_W_LD_WHALF(bA, e_nxt, 0)         // half A of t + 1: lands under the second 48 MFMAs
       e_cur = e_nxt;
-      e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)w_lds_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
+      e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
       if (!HEAD_ROWS) IMF_W_ROWS(rows_nxt, e_nxt)
       __builtin_amdgcn_sched_barrier(0);
       {
@@ -404,21 +373,21 @@ k_spconv_w(const ConvParams p) {
     float4 a0[RB], a1[RB];
 #pragma unroll
     for (int b = 0; b < RB; ++b) {
-      a0[b] = w_lds16(&areg[128 * b + rd_slot]);
-      a1[b] = w_lds16(&areg[128 * b + 64 + rd_slot]);
+      a0[b] = lds_read16(&areg[128 * b + rd_slot]);
+      a1[b] = lds_read16(&areg[128 * b + 64 + rd_slot]);
     }
     if constexpr (AR == kArF32) {
       // B operands: quad (j, cb) of the fp32 image = W[16 j + 4 q4 + t][16 cb + r16], t = 0 .. 3
       float4 b0[4], b1[4];
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
-        b0[cb] = w_lds16(&wreg[cb * 64 + lane]);
-        b1[cb] = w_lds16(&wreg[(4 + cb) * 64 + lane]);
+        b0[cb] = lds_read16(&wreg[cb * 64 + lane]);
+        b1[cb] = lds_read16(&wreg[(4 + cb) * 64 + lane]);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (t + 1 < t1) {
         IMF_W_DMA(e_nxt, rows_nxt)                      // lands under the 128 MFMAs below
-        e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)w_lds_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
+        e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
         IMF_W_ROWS(rows_nxt, e_nxt)
       }
       // k-step (j, t): channel 16 j + 4 q4 + t; sixteen independent accumulators between two MFMAs of one accumulator
@@ -433,21 +402,21 @@ k_spconv_w(const ConvParams p) {
     f16x8 bh[4], bl[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
-      bh[cb] = w_lds_f16x8(&wreg[(2 * cb) * 64 + lane]);
-      bl[cb] = w_lds_f16x8(&wreg[(2 * cb + 1) * 64 + lane]);
+      bh[cb] = lds_read_f16x8(&wreg[(2 * cb) * 64 + lane]);
+      bl[cb] = lds_read_f16x8(&wreg[(2 * cb + 1) * 64 + lane]);
     }
     // every fragment is in registers before the region is refilled
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (t + 1 < t1) {
       IMF_W_DMA(e_nxt, rows_nxt)                      // lands under the 48 MFMAs below
-      e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)w_lds_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
+      e_nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_read_u32(&stab[t + 2 < kSubTab ? t + 2 : kSubTab - 1]));
       IMF_W_ROWS(rows_nxt, e_nxt)
     }
     f16x8 ah[RB], al[RB];
 #pragma unroll
     for (int b = 0; b < RB; ++b) {
       if (PRE) { ah[b] = __builtin_bit_cast(f16x8, a0[b]); al[b] = __builtin_bit_cast(f16x8, a1[b]); }
-      else w_split8(a0[b], a1[b], ah[b], al[b]);
+      else split8(a0[b], a1[b], ah[b], al[b]);
     }
     // per accumulator: lo*hi, hi*lo, hi*hi (k_spconv_g's order); consecutive MFMAs on different accumulators
 #pragma unroll
@@ -504,10 +473,10 @@ k_spconv_w(const ConvParams p) {
       const int row = 16 * b0 + lrow;
       const int col = y * 64 + 4 * c4;
       const int phys = lrow * 16 + (c4 ^ (((lrow >> 2) & 1) << 2));
-      float4 s = w_lds16(&smem[phys]);
+      float4 s = lds_read16(&smem[phys]);
 #pragma unroll
       for (int w = 1; w < W; ++w) {                  // wavefront order: fixed, deterministic
-        const float4 v = w_lds16(&smem[w * REG_F4 + phys]);
+        const float4 v = lds_read16(&smem[w * REG_F4 + phys]);
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
       }
       const int orow = row0 + row < slots_act ? row_of_slot(p, row0 + row) : -1;

@@ -353,8 +353,6 @@ __global__ __launch_bounds__(1024) void k_tsdf_scan(const int32_t *__restrict__ 
   }
 }
 
-inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 // the checks every entry point shares; fills the kernels' parameter block
 int tsdf_params(const char *what, const imf_tsdf_params *p, TsdfP &P) {
   IMF_REQUIRE(p, "%s: null parameters", what);
@@ -385,7 +383,7 @@ extern "C" {
 
 size_t imf_tsdf_allocate_workspace_bytes(int64_t unit_capacity) {
   if (unit_capacity < 1 || unit_capacity > kTsdfMaxUnits) return 0;
-  return al256((size_t)unit_capacity * 8) + al256((size_t)unit_capacity * 4) + 256;
+  return align256((size_t)unit_capacity * 8) + align256((size_t)unit_capacity * 4) + 256;
 }
 
 int imf_tsdf_allocate(const uint16_t *depth, int n_frames, const double *cam2world, const imf_tsdf_params *params,
@@ -413,8 +411,8 @@ int imf_tsdf_allocate(const uint16_t *depth, int n_frames, const double *cam2wor
   hipStream_t st = (hipStream_t)stream;
   char *ws = (char *)workspace;
   uint64_t *keys = (uint64_t *)ws;
-  int32_t *slot_of = (int32_t *)(ws + al256((size_t)unit_capacity * 8));
-  int32_t *n_listed = (int32_t *)(ws + al256((size_t)unit_capacity * 8) + al256((size_t)unit_capacity * 4));
+  int32_t *slot_of = (int32_t *)(ws + align256((size_t)unit_capacity * 8));
+  int32_t *n_listed = (int32_t *)(ws + align256((size_t)unit_capacity * 8) + align256((size_t)unit_capacity * 4));
   const uint32_t capmask = (uint32_t)(table_capacity - 1);
   if (reset) k_tsdf_reset<<<(unsigned)div_up(table_capacity, 256), 256, 0, st>>>(table, table_capacity, n_units);
   const int64_t samples = (int64_t)n_frames * div_up(P.H, stride) * div_up(P.W, stride);
@@ -447,7 +445,7 @@ int imf_tsdf_integrate(const uint16_t *depth, int n_frames, const double *world2
 
 size_t imf_tsdf_extract_workspace_bytes(int64_t max_units) {
   if (max_units < 1 || max_units > kTsdfMaxUnits) return 0;
-  return al256((size_t)max_units * 4) + al256((size_t)(max_units + 1) * 8);
+  return align256((size_t)max_units * 4) + align256((size_t)(max_units + 1) * 8);
 }
 
 int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
@@ -469,7 +467,7 @@ int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n
   hipStream_t st = (hipStream_t)stream;
   char *ws = (char *)workspace;
   int32_t *cnt = (int32_t *)ws;
-  int64_t *offsets = (int64_t *)(ws + al256((size_t)max_units * 4));
+  int64_t *offsets = (int64_t *)(ws + align256((size_t)max_units * 4));
   const uint32_t capmask = (uint32_t)(table_capacity - 1);
   const float2 *vox = reinterpret_cast<const float2 *>(voxels);
   k_tsdf_extract<false><<<(unsigned)max_units, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, cnt,
