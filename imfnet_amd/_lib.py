@@ -37,9 +37,8 @@ class ConvArgs(C.Structure):
         ("out", C.c_void_p),
         ("split_k", C.c_int32), ("variant", C.c_int32),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-        ("tickets", C.c_void_p),
         ("ev_begin", C.c_void_p), ("ev_end", C.c_void_p),
-        ("n_out_dev", C.c_void_p), ("dyn_split_kvol", C.c_int32), ("slots_extra", C.c_int32),
+        ("n_out_dev", C.c_void_p), ("slots_extra", C.c_int32),
         ("kernel_tag", C.c_int32), ("dyn_err", C.c_void_p), ("geglu", C.c_int32), ("operand_format", C.c_int32),
     ]
 
@@ -288,8 +287,6 @@ SIGNATURES = {
     "imf_packed_weight_floats_bf16x3": (_L, [_I, _I, _I]),
     "imf_pack_weights_bf16x3": (_I, [_P, _I, _I, _I, _P, _P]),
     "imf_spconv_auto_split": (_I, [_L, _I, _I]),
-    "imf_spconv_max_split": (_I, [_I, _I]),
-    "imf_spconv_occupancy": (_I, [_I, _I, _I]),
     "imf_spconv_workspace_bytes": (_Z, [_L, _I, _I]),
     "imf_spconv_fwd": (_I, [C.POINTER(ConvArgs), _P]),
     "imf_pointwise_head": (_I, [C.POINTER(HeadArgs), _P]),

@@ -15,7 +15,7 @@ void set_error(const char *fmt, ...) {
 }  // namespace imf
 
 extern "C" {
-int imf_version(void) { return 100; }   /* 0.1.0 */
+int imf_version(void) { return 101; }   /* 0.1.1: imf_conv_args lost two fields */
 const char *imf_last_error(void) { return imf::g_err; }
 
 void *imf_event_create(void) {

@@ -7,11 +7,12 @@
 //
 // Two modes:
 //   exact     the row count of every level is known on the host (one D2H readback after the pyramid build);
-//             arenas, grids and split-K partitions are sized for exactly those rows.
+//             arenas and grids are sized for exactly those rows.
 //   capacity  (io->dyn) nothing is read back: arenas, rulebooks and grids are sized for CAPACITIES, the kernels
-//             take the actual counts from the pyramid's device meta block, and the per-launch choices that depend
-//             on the row count (split-K partitions, fusion hidden-split) are made on the device with the same rule
-//             as the host -- so a capacity-mode forward is bit-identical to the exact one.  Because every address,
+//             take the actual counts from the pyramid's device meta block.  Every convolution is an unsplit launch
+//             in both modes (its kernel is a function of the level and the layer's channels only), and the one
+//             choice that depends on the row count (the fusion block's hidden split) is made on the device with the
+//             host's rule -- so a capacity-mode forward is bit-identical to the exact one.  Because every address,
 //             grid and argument is then a function of the capacities only, the whole fragment
 //             (imf_fragment_forward: pyramid + rulebooks + image branch + 23 convolutions + fusion) can be
 //             captured ONCE per capacity bucket as a hipGraph and replayed with no host work but one launch.
@@ -29,14 +30,14 @@ struct Rb {   // rulebook inside the int arena
   int32_t *tile_rows = nullptr, *nbr = nullptr;
   uint32_t *tile_mask = nullptr;
   int64_t n_slots = 0, n_out = 0;
-  int kvol = 1, max_active = 1;
+  int kvol = 1;
   int level = 0;          // pyramid level of the OUTPUT rows (row count: meta[2 * level] in capacity mode)
   int slots_extra = 0;    // parity-class padding of transposed maps (slots beyond roundup64(rows))
   int side_piece = 0;     // the piece of the side chain that builds it (SideChain): 1 .. 3 = level, 4 = the tail, 0 = none
   int ready_event = -1;   // index into io->events that the main stream must wait on before first use
   // the map's shape, and its tables from byte address p on; returns the first byte behind them
-  uintptr_t place(uintptr_t p, int64_t slots, int64_t rows, int kvol_, int max_active_, int level_, int side_piece_) {
-    n_slots = slots; n_out = rows; kvol = kvol_; max_active = max_active_; level = level_; side_piece = side_piece_;
+  uintptr_t place(uintptr_t p, int64_t slots, int64_t rows, int kvol_, int level_, int side_piece_) {
+    n_slots = slots; n_out = rows; kvol = kvol_; level = level_; side_piece = side_piece_;
     const size_t tables = (size_t)n_slots + (size_t)kvol * n_slots;
     tile_rows = (int32_t *)p;
     nbr = (int32_t *)(p + 4 * (size_t)n_slots);
@@ -79,16 +80,16 @@ inline int dbuf(int i, int s) { return D0A + 3 * i + s; }
 // its totals, imf_resunet_forward and imf_fragment_forward take every pointer from it.
 //   int arena    [256-byte aligned] first map (rulebook first convolution only) | k3[0..3] | dn[0..2] | up[0..2] | k3s[0..2]
 //                | sort workspace (256-byte aligned inside 64 words of slack) | 3 x 16 counters | bit grid
-//   float arena  [256-byte aligned] NBUF feature buffers, each rounded up to 64 floats | convolution workspace | fusion
-//                workspace (256-byte aligned, 64 floats below the end) -- the convolution workspace takes the slack between
+//   float arena  [256-byte aligned] NBUF feature buffers, each rounded up to 64 floats | alignment slack | fusion
+//                workspace (256-byte aligned, 64 floats below the end).  No convolution workspace: every launch is unsplit.
 struct Layout {
   Rb first, k3[4], dn[3], up[3];   // conv1's map; stride-1 maps; strided maps INTO level i + 1; transposed maps into level i
   Rb k3s[3], id;                   // occupancy-sorted twins of k3[0..2] (csrc/rulebook_sort.hip); pointwise layers: no tables
   int32_t *sort_ws, *counters;     // ONE workspace for the sorts (their stream runs them in turn); 16 words per transposed map
   uint32_t *bitgrid;               // conv1's occupancy grid
   size_t sort_ws_bytes, bitgrid_words, int_bytes;
-  float *buf[NBUF], *conv_ws, *fusion_ws;   // conv_ws: split-K partials or the balanced tail's
-  size_t buf_floats[NBUF], conv_ws_bytes, fusion_ws_bytes, float_bytes;
+  float *buf[NBUF], *fusion_ws;
+  size_t buf_floats[NBUF], fusion_ws_bytes, float_bytes;
 };
 
 // `capacity`: the fusion workspace of capacity mode.  The arenas may be null (the sizing entry points): the totals do not
@@ -97,14 +98,14 @@ Layout arena_layout(const Sizes &s, bool capacity, size_t bitgrid_words, const v
   Layout l;
   const uintptr_t ibase = align256((uintptr_t)int_arena);
   uintptr_t p = ibase;
-  if (!s.small_first) p = l.first.place(p, s.slots[0], s.n[0], s.first_kvol, s.first_kvol, 0, 0);
-  for (int i = 0; i < 4; ++i) p = l.k3[i].place(p, s.slots[i], s.n[i], 27, 27, i, i);
-  for (int i = 0; i < 3; ++i) p = l.dn[i].place(p, s.slots[i + 1], s.n[i + 1], 27, 27, i + 1, i + 1);
+  if (!s.small_first) p = l.first.place(p, s.slots[0], s.n[0], s.first_kvol, 0, 0);
+  for (int i = 0; i < 4; ++i) p = l.k3[i].place(p, s.slots[i], s.n[i], 27, i, i);
+  for (int i = 0; i < 3; ++i) p = l.dn[i].place(p, s.slots[i + 1], s.n[i + 1], 27, i + 1, i + 1);
   for (int i = 0; i < 3; ++i) {
-    p = l.up[i].place(p, s.up_slots[i], s.n[i], 27, 8, i, 4);
+    p = l.up[i].place(p, s.up_slots[i], s.n[i], 27, i, 4);
     l.up[i].slots_extra = 8 * IMF_TILE_ROWS;
   }
-  for (int i = 0; i < 3; ++i) p = l.k3s[i].place(p, s.slots[i], s.n[i], 27, 27, i, i);
+  for (int i = 0; i < 3; ++i) p = l.k3s[i].place(p, s.slots[i], s.n[i], 27, i, i);
   l.sort_ws = (int32_t *)align256(p);
   l.sort_ws_bytes = imf_rulebook_sorted_workspace_bytes(s.slots[0]);
   p += 4 * (64 /* alignment slack */ + l.sort_ws_bytes / 4);
@@ -127,13 +128,9 @@ Layout arena_layout(const Sizes &s, bool capacity, size_t bitgrid_words, const v
     l.buf[i] = (float *)(fbase + 4 * floats);
     floats += (l.buf_floats[i] + 63) / 64 * 64;
   }
-  l.conv_ws = (float *)(fbase + 4 * floats);
-  // Every launch is unsplit (one workgroup owns a tile for all offsets; imf_spconv_workspace_bytes(.., 1) == 0): the
-  // convolution workspace (the optional balanced tail's) is the slack below, nothing is reserved for it.
   l.fusion_ws_bytes = (capacity ? imf_fusion_workspace_bytes_cap(s.n[3]) : imf_fusion_workspace_bytes(s.n[3])) / 4 * 4;
   l.float_bytes = floats * 4 + l.fusion_ws_bytes + 2048;   // alignment slack of the three carved regions
   l.fusion_ws = (float *)(((uintptr_t)float_arena + l.float_bytes - l.fusion_ws_bytes - 256) & ~(uintptr_t)255);
-  l.conv_ws_bytes = (size_t)((char *)l.fusion_ws - (char *)l.conv_ws);
   return l;
 }
 
@@ -498,7 +495,6 @@ int launch_step(const Forward &f, const Layout &l, const Step &st, SideChain &ch
   a.split_k = 1;
   a.kernel_tag = imf_resunet_conv_kernel_tag(rb.level, c.kvol, c.cin, c.cout, c.variant, io->n_items);
   a.variant = c.variant;
-  a.workspace = l.conv_ws; a.workspace_bytes = l.conv_ws_bytes;
   IMF_REQUIRE(st.in_b < 0 || fmt.of(st.in_a) == fmt.of(st.in_b), "imf_resunet_forward: conv %d concatenates an operand "
               "image with an fp32 buffer", st.conv);
   const bool out_split = fmt.wants_split(st.out) && !c.l2norm;

@@ -247,28 +247,6 @@ k_spconv_mfma(const ConvParams p) {
         p.partial[((long long)z * p.n_slots + slot) * p.cout + col] = acc[cb][r];
       }
     }
-    if (p.tickets) {
-      // In-launch split-K combine, placement-independent (cdna_hip_programming.md G16, counter form):
-      // every storing wave drains, ONE lane releases at agent scope and takes a ticket; the last
-      // arriver acquires at agent scope, then all its waves read the S slabs with plain loads.
-      __shared__ int s_last;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int *cnt = p.tickets + (long long)tile * gridDim.y + y;
-        const int t = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (t == S - 1);
-        if (last) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-        }
-        s_last = last;
-      }
-      __syncthreads();
-      if (s_last) fused_reduce_tile<16 * CO_BLK>(p, S, tile_slot0, y, tid);
-    }
   }
 }
 
@@ -277,12 +255,6 @@ k_spconv_mfma(const ConvParams p) {
 // One thread per (slot, 4 output channels).
 __global__ void __launch_bounds__(256)
 k_spconv_reduce(const ConvParams p, int S) {
-  if (p.n_out_dev && p.dyn_split_kvol) {   // capacity mode: the main kernel chose the split from the actual rows
-    const int cover = S;
-    S = auto_split_rule(conv_slots(p, conv_rows(p)), p.cout, p.dyn_split_kvol, p.split_min_blocks, p.split_target);
-    S = S > cover ? cover : S;
-    if (S == 1) return;                    // unsplit: the main kernel already wrote the output
-  }
   const int c4n = p.cout / 4;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long slot = idx / c4n;
@@ -349,29 +321,17 @@ int imf_pack_weights(const float *w, int kvol, int cin, int cout, float *packed,
     else X(K<2, 2>);                        \
   } while (0)
 
-/* Resident workgroups per CU the runtime reports for a sparse-conv kernel instantiation (tuning aid). */
-int imf_spconv_occupancy(int variant, int co_blk, int j) {
-  int n = -1;
-  const void *f = nullptr;
-#define IMF_ADDRESS(...) f = (const void *)__VA_ARGS__
-  if (variant == 0) IMF_CB_J(k_spconv_mfma, co_blk, j, IMF_ADDRESS);
-  else if (variant == 1) IMF_CB_J(k_spconv_mfma_simple, co_blk, j, IMF_ADDRESS);
-  else return -1;
-#undef IMF_ADDRESS
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess) return -1;
-  return n;
-}
-
 constexpr int kSplitMinBlocks = 400;   // measured: 438 unsplit workgroups (a pair's stride-2 level) beat split 2 + reduce by 1.5 % per step
 constexpr int kSplitTarget = 768;      // (round-1 values; 512 ... 1536 measured in round 2)
 
 int imf_spconv_auto_split(int64_t n_slots, int cout, int kvol) {
-  return auto_split_rule(n_slots, cout, kvol, kSplitMinBlocks, kSplitTarget);
-}
-
-/* Largest split the rule can return for any row count up to the capacity (fewer rows -> more partitions). */
-int imf_spconv_max_split(int cout, int kvol) {
-  return auto_split_rule(IMF_TILE_ROWS, cout, kvol, kSplitMinBlocks, kSplitTarget);
+  if (kvol <= 1 || kvol >= 28) return 1;
+  const long long blocks = (n_slots / IMF_TILE_ROWS) * (cout / (16 * co_blk_of(cout)));
+  if (blocks >= kSplitMinBlocks || blocks <= 0) return 1;
+  long long s = (kSplitTarget + blocks - 1) / blocks;
+  if (s > 8) s = 8;
+  if (s > kvol / 2) s = kvol / 2;
+  return s < 1 ? 1 : (int)s;
 }
 
 size_t imf_spconv_workspace_bytes(int64_t n_slots, int cout, int split) {
@@ -395,71 +355,71 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   IMF_REQUIRE(!a->l2norm || a->cout == 16 * CB, "imf_spconv_fwd: l2norm needs cout in {32, 64}");
   IMF_REQUIRE(a->variant == 0 || a->variant == 1 || a->variant == 3 || a->variant == 6,
               "imf_spconv_fwd: variant=%d (0 = fp32 MFMA, 1 = fp32 MFMA without the pipeline, 3 = bf16x3 MFMA, 6 = split-f16 MFMA)", a->variant);
+  // ---- the route: which kernel family, how many kernel-offset partitions ----
+  const bool regs = (a->kernel_tag & IMF_TAG_REGS) != 0;
   const bool v16 = a->variant == 6 || a->variant == 3;   // the 16-bit matrix pipe: LDS-DMA kernels only
+  // variants 0 / 1 without any pipeline: variant 1, maps of 28 offsets or more, a (k, cc) chunk that would straddle the two sources
   const bool simple = !v16 && (a->variant == 1 || a->kvol >= kKCache || (a->c_b > 0 && a->c_a % (16 * J) != 0));
-  IMF_REQUIRE(!v16 || a->kvol < kKCache,
-              "imf_spconv_fwd: variants 6 / 3 (split-f16 / bf16x3 weights) need kvol <= %d", kKCache - 1);
-  IMF_REQUIRE(!v16 || (a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024),
-              "imf_spconv_fwd: variants 6 / 3 need kvol * cin / 32 < %d and <= 1024 channels per source (kvol=%d cin=%d): use variant 0",
-              kSubTab, a->kvol, cin);
-  IMF_REQUIRE(a->variant != 3 || (!(a->kernel_tag & IMF_TAG_REGS) && !a->tickets), "imf_spconv_fwd: variant 3 has no register-staged kernel / tickets");
   // Variant 0 (fp32 MFMA) runs on the LDS-DMA kernels too (k_spconv_g / k_spconv_w with AR = kArF32: the fp32 weight image
-  // has the split-f16 image's sub-stage addressing) wherever their tables cover the shape; IMF_TAG_REGS or `tickets` keep
-  // the register-staged kernel k_spconv_mfma (A/B, the in-launch split-K combine).
-  const bool dma0 = a->variant == 0 && !simple && !(a->kernel_tag & IMF_TAG_REGS) && !a->tickets && a->kvol < kKCache &&
-                    a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024;
+  // has the split-f16 image's sub-stage addressing) wherever their tables cover the shape; IMF_TAG_REGS keeps the
+  // register-staged kernel k_spconv_mfma (A/B, inputs beyond the 2 GiB buffer window).
+  const bool dma0 = a->variant == 0 && !simple && !regs && a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024;
   const bool dma = v16 || dma0;
   // the wave-split kernel (spconv_w.hip): the whole unit of rows in one workgroup, no split-K partitions, no reduce launch
   const bool wsplit = dma && (a->kernel_tag & (IMF_TAG_WAVE8 | IMF_TAG_WAVE4));
+  const int split = (simple || wsplit) ? 1 : (a->split_k > 0 ? a->split_k : imf_spconv_auto_split(a->n_slots, a->cout, a->kvol));
+
+  // ---- what the route asks of the arguments ----
+  if (v16) {
+    IMF_REQUIRE(a->kvol < kKCache, "imf_spconv_fwd: variants 6 / 3 (split-f16 / bf16x3 weights) need kvol <= %d", kKCache - 1);
+    IMF_REQUIRE(a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024,
+                "imf_spconv_fwd: variants 6 / 3 need kvol * cin / 32 < %d and <= 1024 channels per source (kvol=%d cin=%d): use variant 0",
+                kSubTab, a->kvol, cin);
+    IMF_REQUIRE(a->variant != 3 || !regs, "imf_spconv_fwd: variant 3 has no register-staged kernel");
+  }
   if (wsplit) {
     IMF_REQUIRE(a->cout % 64 == 0 && (a->kvol > 1 || cin >= 256),
                 "imf_spconv_fwd: the wave-split kernel needs cout %% 64 == 0 and kvol > 1 or cin >= 256 (kvol=%d cin=%d cout=%d)",
                 a->kvol, cin, a->cout);
-    IMF_REQUIRE(a->split_k <= 1 && !a->tickets, "imf_spconv_fwd: the wave-split kernel takes no split_k / tickets");
+    IMF_REQUIRE(a->split_k <= 1, "imf_spconv_fwd: the wave-split kernel takes no split_k");
   }
-  int split = (simple || wsplit) ? 1 : (a->split_k > 0 ? a->split_k : imf_spconv_auto_split(a->n_slots, a->cout, a->kvol));
   IMF_REQUIRE(split >= 1 && split <= 32, "imf_spconv_fwd: split_k=%d", split);
+  IMF_REQUIRE(!a->n_out_dev || split == 1,
+              "imf_spconv_fwd: n_out_dev (capacity mode) needs an unsplit launch (split_k = 1), got split_k=%d", split);
   if (split > 1)
     IMF_REQUIRE(a->workspace && a->workspace_bytes >= imf_spconv_workspace_bytes(a->n_slots, a->cout, split),
                 "imf_spconv_fwd: split_k=%d needs %zu workspace bytes", split,
                 imf_spconv_workspace_bytes(a->n_slots, a->cout, split));
+  IMF_REQUIRE(!a->operand_format || (a->variant == 6 && split == 1 && !regs),
+              "imf_spconv_fwd: operand_format needs variant 6 and an unsplit launch (split_k=%d)", split);
+  IMF_REQUIRE(!(a->operand_format & IMF_FMT_OUT_SPLIT) || !a->l2norm, "imf_spconv_fwd: IMF_FMT_OUT_SPLIT not with l2norm");
+  IMF_REQUIRE(!(a->operand_format & IMF_FMT_RES_SPLIT) || a->residual, "imf_spconv_fwd: IMF_FMT_RES_SPLIT without a residual");
+  IMF_REQUIRE(!a->geglu || ((v16 || (a->variant == 0 && !simple)) && !wsplit && a->kvol == 1 && a->cout % 64 == 0 &&
+                            split == 1 && !a->scale && !a->residual && !a->relu && !a->l2norm && (dma0 || !regs)),
+              "imf_spconv_fwd: geglu needs variant 6 (k_spconv_g) or 0, kvol 1, cout %% 64 == 0, an unsplit launch and no other epilogue");
+  if (a->variant == 6 && regs) {
+    set_error("imf_spconv_fwd: variant 6 has no register-staged kernel (IMF_TAG_REGS): it belongs to variant 0");
+    return IMF_EUNSUPPORTED;
+  }
+
   ConvParams p{a->in_a, a->in_b, a->c_a, a->c_b, a->w_packed, a->kvol, a->cout, a->tile_rows,
                a->nbr, a->tile_mask, (long long)a->n_slots, (long long)a->n_out, a->scale, a->shift,
-               a->residual, a->relu, a->l2norm, a->out, (float *)a->workspace,
-               (a->variant == 0 && !simple) ? a->tickets : nullptr};
+               a->residual, a->relu, a->l2norm, a->out, (float *)a->workspace};
   p.w_unscale = a->variant == 6 ? a->w_packed + (long long)a->kvol * cin * a->cout + 1 : nullptr;
   p.arith = a->variant == 6 ? kArF16x2 : (a->variant == 3 ? kArBf16x3 : kArF32);
   p.n_out_dev = a->n_out_dev;
-  p.dyn_split_kvol = (a->n_out_dev && !wsplit) ? a->dyn_split_kvol : 0;
   p.slots_extra = a->slots_extra;
-  p.split_min_blocks = kSplitMinBlocks;
-  p.split_target = kSplitTarget;
-  IMF_REQUIRE(!a->n_out_dev || dma || split == 1,
-              "imf_spconv_fwd: n_out_dev (capacity mode) on the fp32-MFMA kernels needs an unsplit launch (split_k = 1)");
   p.err = a->dyn_err;
   p.geglu = a->geglu;
   p.a_split = (a->operand_format & IMF_FMT_A_SPLIT) ? 1 : 0;
   p.res_split = (a->operand_format & IMF_FMT_RES_SPLIT) ? 1 : 0;
   p.out_split = (a->operand_format & IMF_FMT_OUT_SPLIT) ? 1 : 0;
-  IMF_REQUIRE(!a->operand_format || (a->variant == 6 && split == 1 && !a->tickets && !(a->kernel_tag & IMF_TAG_REGS)),
-              "imf_spconv_fwd: operand_format needs variant 6 and an unsplit launch (split_k=%d)", split);
-  IMF_REQUIRE(!p.out_split || !a->l2norm, "imf_spconv_fwd: IMF_FMT_OUT_SPLIT not with l2norm");
-  IMF_REQUIRE(!p.res_split || a->residual, "imf_spconv_fwd: IMF_FMT_RES_SPLIT without a residual");
-  IMF_REQUIRE(!a->geglu || ((v16 || (a->variant == 0 && !simple)) && !wsplit && a->kvol == 1 && a->cout % 64 == 0 &&
-                            split == 1 && !a->scale && !a->residual && !a->relu && !a->l2norm && (dma0 || !(a->kernel_tag & IMF_TAG_REGS))),
-              "imf_spconv_fwd: geglu needs variant 6 (k_spconv_g) or 0, kvol 1, cout %% 64 == 0, an unsplit launch and no other epilogue");
   // XCD-contiguous tile order of k_spconv_g: workgroup b runs on XCD b % 8 and every XCD has its own 4 MiB L2, so XCD x
   // walks ONE range of consecutive tiles (cut from the actual tiles on the device; grid.x padded to a multiple of 8) and its
   // L2 serves ~1/8 of the input rows.  Same sums.  Not for parity-grouped transposed maps, whose consecutive tiles are one
   // parity class spread over the whole level.  Measurements: LAB_NOTES.md 4h-h.
   const bool g_xcd = dma && !wsplit && a->n_slots == imf_rulebook_slots(a->n_out);
   p.no_xcd_swizzle = !g_xcd;
-  IMF_REQUIRE(!p.dyn_split_kvol || (!p.tickets && a->split_k >= 1), "imf_spconv_fwd: dyn_split_kvol needs an explicit split_k cover and no tickets");
-  if (a->variant == 6 && ((a->kernel_tag & IMF_TAG_REGS) || a->tickets)) {
-    set_error("imf_spconv_fwd: variant 6 has no register-staged kernel (IMF_TAG_REGS) and no in-launch combine (tickets): "
-              "both belong to variant 0");
-    return IMF_EUNSUPPORTED;
-  }
   dim3 grid((unsigned)(a->n_slots / IMF_TILE_ROWS), (unsigned)(a->cout / (16 * CB)), (unsigned)split);
   if (g_xcd) grid.x = (grid.x + 7u) / 8u * 8u;
   hipStream_t st = (hipStream_t)stream;
@@ -476,7 +436,7 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   }
   IMF_CHECK_LAUNCH("k_spconv_mfma");
   if (a->ev_end) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)a->ev_end, st));
-  if (split > 1 && !p.tickets) {
+  if (split > 1) {
     const long long total = (long long)a->n_slots * (a->cout / 4);
     k_spconv_reduce<<<(unsigned)div_up(total, 256), 256, 0, st>>>(p, split);
     IMF_CHECK_LAUNCH("k_spconv_reduce");

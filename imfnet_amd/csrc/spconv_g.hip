@@ -25,7 +25,7 @@
 // (checked on the hardware by the micro-benchmark).  Everything lives in ONE __shared__ array: with a second
 // object hipcc 7.2 drains the DMA queue before every ds_read.
 //
-// Not covered here: the in-launch split-K combine (tickets) -- variant 0's register-staged k_spconv_mfma (spconv.hip) has it.
+// Not covered here: inputs beyond the 2 GiB buffer window -- variant 0's register-staged k_spconv_mfma (spconv.hip) serves them.
 #include "spconv_shared.h"
 
 #ifndef IMF_G_ABL
@@ -118,7 +118,8 @@ k_spconv_g(const ConvParams p) {
 #define IMF_WBUF(b) (WS1 ? smem : smem + (b) * BUF_F4)
 #define IMF_ABUF(b) (WS1 ? smem + SUB_F4 + (b) * (4 * AW_F4) + wave * AW_F4 : smem + (b) * BUF_F4 + SUB_F4 + wave * AW_F4)
 
-  int super = blockIdx.x, z = blockIdx.z, S = gridDim.z;
+  int super = blockIdx.x;
+  const int z = blockIdx.z, S = gridDim.z;
   long long slots_act = p.n_slots;
   if (p.n_out_dev) slots_act = conv_slots(p, conv_rows(p));   // capacity mode: the actual rows
   if (!p.no_xcd_swizzle && (gridDim.x & 7u) == 0) {
@@ -133,17 +134,7 @@ k_spconv_g(const ConvParams p) {
     if ((unsigned)super >= t_act) return;
   }
   const int tile0 = super * RB;
-  if (p.n_out_dev) {   // capacity mode: padding tiles leave; the split is the rule applied to the actual rows
-    if ((long long)tile0 * IMF_TILE_ROWS >= slots_act) return;
-    if (p.dyn_split_kvol) {
-      S = auto_split_rule(slots_act, p.cout, p.dyn_split_kvol, p.split_min_blocks, p.split_target);
-      if (S > (int)gridDim.z) {
-        if (p.err && blockIdx.x == 0 && blockIdx.y == 0 && z == 0 && threadIdx.x == 0) atomicOr(p.err, 16);
-        S = gridDim.z;
-      }
-      if (z >= S) return;
-    }
-  }
+  if (p.n_out_dev && (long long)tile0 * IMF_TILE_ROWS >= slots_act) return;   // capacity mode: padding tiles leave
   const int y = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, q4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -495,19 +486,15 @@ void launch_spconv_g(const ConvParams &p, dim3 grid, int co_blk, hipStream_t st,
   // deep ring (NB 4, two workgroups per CU) when the whole launch is resident at once that way (<= 512 workgroups);
   // measured (tools/layer_times.py): 438 unsplit workgroups of a pair's stride-2 level 43 -> 33 us, but 544 workgroups
   // 28 -> 33 us (a second round of 32), and every launch that fills the chip is faster with four workgroups per CU
-  const int nb_env = 0, nb_wgs = 512;   // ring depth: by size (the deep ring when the whole launch is resident, <= 512 workgroups)
   long long wgs = (long long)grid.x * grid.y * grid.z;
   if (p.n_out_dev) {
-    // capacity mode: the grid covers a capacity and the largest split, the working workgroups are decided on the
+    // capacity mode (unsplit: grid.z == 1): the grid covers a capacity, the working workgroups are decided on the
     // device.  Estimate them the way the buckets are sized (rows ~ capacity / 1.2; model/graph.py) -- a wrong guess
     // costs time only, both ring depths form the same sums.
     const long long tiles = grid.x > 1 ? (long long)(grid.x / 1.2) : 1;
-    const int s_est = p.dyn_split_kvol ? auto_split_rule(tiles * IMF_TILE_ROWS, p.cout, p.dyn_split_kvol,
-                                                         p.split_min_blocks, p.split_target)
-                                       : (int)grid.z;
-    wgs = tiles * grid.y * (s_est < (int)grid.z ? s_est : (int)grid.z);
+    wgs = tiles * grid.y;
   }
-  const bool deep = nb_env ? nb_env >= 4 : wgs <= nb_wgs;
+  const bool deep = wgs <= 512;   // ring depth by size: the deep ring when the whole launch is resident
   // launches that fill the chip.  bf16x3: single buffers (WS1: 5 / 7 workgroups per CU instead of 3 / 4).  Split-f16 and fp32
   // (8 / 4 KiB weight blocks, four per CU with the ring of two already): single buffers for the 32-column slabs only -- A/B
   // on one box, 32 -> 32 at 103 k rows 38.5 -> 36.8 us (f16x2), 67.8 -> 65.3 us (fp32; in situ 52.2 -> 48.7), but 64 -> 64

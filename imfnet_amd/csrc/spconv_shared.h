@@ -49,19 +49,14 @@ struct ConvParams {
   int relu, l2norm;
   float *out;
   float *partial;   // split-K partial sums [S][n_slots][cout] (S = gridDim.z > 1)
-  int *tickets;     // optional arrival counters [n_tiles][n_slabs] (zero on entry, left zero): the last
-                    // partition to arrive reduces the tile in-kernel instead of a second launch
   // variant 6: the split-f16 weight image is stored scaled by a power of two (so that the lo halves stay
   // normal f16 numbers); *w_unscale = 2^-s is multiplied back into the fp32 accumulators (exact).  NULL = 1.
   const float *w_unscale;
   // Capacity mode (whole-forward graphs): n_slots / n_out are capacities, the actual row count lives on the
-  // device.  Tiles beyond the actual slots exit at once; with dyn_split_kvol != 0 the number of kernel-offset
-  // partitions is the automatic rule evaluated on the ACTUAL rows (gridDim.z covers the largest it can return),
-  // so the sums are formed exactly as by an exact-size launch.
+  // device.  Tiles beyond the actual slots exit at once; the launch is unsplit (imf_spconv_fwd), so the sums are
+  // formed exactly as by an exact-size unsplit launch.
   const int32_t *n_out_dev;
-  int dyn_split_kvol;       // third argument of the split rule (active offsets per tile); 0 = gridDim.z is the split
   int slots_extra;          // slots the rulebook lays out beyond roundup64(rows): 0, or 512 for transposed maps
-  int split_min_blocks, split_target;
   int no_xcd_swizzle;       // k_spconv_g: plain blockIdx.x -> tile order instead of one range of consecutive tiles per XCD
                             // (imf_spconv_fwd: wave-split launches, transposed maps)
   int w_xcd;                // k_spconv_w's workgroup order: 2 = slab by XCD and one range of consecutive tiles per XCD,
@@ -81,8 +76,7 @@ struct ConvParams {
   int res_split;            // `residual` is an operand image
   int out_split;            // write `out` as an operand image (not with l2norm / geglu)
   int arith;                // kArF16x2 (with a_split: kArF16x2Pre) or kArF32: which weight image w_packed is and which MFMAs run
-  int32_t *err;             // flag word (optional): 16 = the rule wanted more partitions than the launch covers
-                            // (capacity mode); 32 = an output value left the f16 range (|y| >= 65504 or NaN): the
+  int32_t *err;             // flag word (optional): 32 = an output value left the f16 range (|y| >= 65504 or NaN): the
                             // next split-f16 convolution would turn it into inf -- see IMF_FLAG_RANGE
 };
 
@@ -92,17 +86,6 @@ __device__ __forceinline__ bool range_guard(const ConvParams &p) { return p.err 
 constexpr float kF16Max = 65504.f;
 // true when y cannot be carried by the split-f16 operands of the next convolution (also for NaN)
 __device__ __forceinline__ bool out_of_f16_range(float y) { return !(fabsf(y) < kF16Max); }
-
-// The automatic split-K rule (imf_spconv_auto_split), shared by host and device.
-__host__ __device__ inline int auto_split_rule(long long n_slots, int cout, int kvol, int min_blocks, int target) {
-  if (kvol <= 1 || kvol >= 28) return 1;
-  const long long blocks = (n_slots / IMF_TILE_ROWS) * (cout / (16 * ((cout % 64 == 0) ? 4 : 2)));
-  if (blocks >= min_blocks || blocks <= 0) return 1;
-  long long s = (target + blocks - 1) / blocks;
-  if (s > 8) s = 8;
-  if (s > kvol / 2) s = kvol / 2;
-  return s < 1 ? 1 : (int)s;
-}
 
 // actual rows / slots of a launch (capacity mode reads them from the device)
 __device__ __forceinline__ long long conv_rows(const ConvParams &p) {
@@ -326,47 +309,6 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvParams &p, const 
     }
   }
   if (range_guard(p) && __ballot(bad) != 0ull && lane == 0) atomicOr(p.err, 32);
-}
-
-// Sum of the S partial slabs of one 64-row tile (ascending partition order) + epilogue, by the 256
-// threads of the LAST workgroup to arrive at the tile (same arithmetic as k_spconv_reduce).
-template <int CW>
-__device__ __forceinline__ void fused_reduce_tile(const ConvParams &p, int S, long long slot0, int y, int tid) {
-  constexpr int LPR = CW / 4, RPI = 256 / LPR;
-  const int c4 = tid % LPR, rsub = tid / LPR;
-  const int col = y * CW + 4 * c4;
-  float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p.scale) sc = *reinterpret_cast<const float4 *>(p.scale + col);
-  if (p.shift) sh = *reinterpret_cast<const float4 *>(p.shift + col);
-  const float un = p.w_unscale ? *p.w_unscale : 1.f;
-#pragma unroll 1
-  for (int it = 0; it < IMF_TILE_ROWS / RPI; ++it) {
-    const long long slot = slot0 + it * RPI + rsub;
-    const int orow = row_of_slot(p, slot);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (orow >= 0) {
-      for (int zz = 0; zz < S; ++zz) {
-        const float4 v = *reinterpret_cast<const float4 *>(p.partial + ((long long)zz * p.n_slots + slot) * p.cout + col);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-      }
-      s.x = (s.x * un) * sc.x + sh.x; s.y = (s.y * un) * sc.y + sh.y; s.z = (s.z * un) * sc.z + sh.z; s.w = (s.w * un) * sc.w + sh.w;
-      if (p.residual) {
-        const float4 rr = *reinterpret_cast<const float4 *>(p.residual + (long long)orow * p.cout + col);
-        s.x += rr.x; s.y += rr.y; s.z += rr.z; s.w += rr.w;
-      }
-      if (p.relu) { s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f); }
-      if (range_guard(p) && (out_of_f16_range(s.x) || out_of_f16_range(s.y) || out_of_f16_range(s.z) || out_of_f16_range(s.w)))
-        atomicOr(p.err, 32);
-    }
-    if (p.l2norm) {
-      float ss = s.x * s.x + s.y * s.y + s.z * s.z + s.w * s.w;
-#pragma unroll
-      for (int o = 1; o < LPR; o <<= 1) ss += __shfl_xor(ss, o, 64);
-      const float nrm = sqrtf(ss);
-      s.x /= nrm; s.y /= nrm; s.z /= nrm; s.w /= nrm;
-    }
-    if (orow >= 0) *reinterpret_cast<float4 *>(p.out + (long long)orow * p.cout + col) = s;
-  }
 }
 
 constexpr int kKCache = 28;   // active offsets cached per workgroup (kvol <= 27 uses the pipelined kernels)

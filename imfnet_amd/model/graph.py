@@ -4,8 +4,8 @@ capacity mode, captured once per capacity bucket as a hipGraph and replayed per 
 The exact path (extract.py -> ResUNet2.forward -> NativePlan) reads the four level counts back after the
 pyramid build and spends ~0.5 ms of host time enqueueing ~150 launches per fragment.  Here every buffer,
 rulebook and grid is sized for a CAPACITY; the kernels read the actual counts from the pyramid's device meta
-block and take the row-count-dependent decisions (split-K partitions, fusion hidden split) on the device with the
-host's rule, so the descriptors are bit-identical to the exact path.  Per fragment the host writes 16 ints (point
+block; every convolution is an unsplit launch in both paths, and the one row-count-dependent decision (the fusion
+block's hidden split) is taken on the device with the host's rule, so the descriptors are bit-identical to the exact path.  Per fragment the host writes 16 ints (point
 count, item starts), the inputs land in the bucket's static buffers, and ONE hipGraphLaunch runs
 util/misc.py:82-104 + model/resunet.py:163-235 end to end.  The counts come back with the descriptors.
 
@@ -25,7 +25,7 @@ from .._lib import DYN_WORDS, META_WORDS, FragmentCaps, FragmentIO, ImfError, MA
 from .plan import arm_trace, fp32_buffers, trace_records
 
 FLAG_NAMES = {1: "coordinate out of range", 2: "a level exceeded its row capacity", 4: "bounding box exceeds the bit grid",
-              8: "an item has no voxel", 16: "far fewer rows than the capacity (split cover)"}
+              8: "an item has no voxel"}      # 16: retired (include/imfnet_hip.h), not to be reused
 
 
 def _grid_up(v, ratio, lo):

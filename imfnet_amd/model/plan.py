@@ -153,7 +153,6 @@ class FusedPlan:
         a.split_k = split
         a.kernel_tag = self.L.imf_resunet_conv_kernel_tag(rb.level, a.kvol, c_a + c_b, a.cout, a.variant, self._n_items)
         a.workspace, a.workspace_bytes = (ws[0] or None, ws[1])
-        a.tickets = None
         a.dyn_err = self._flags if (a.variant == 6 and not a.l2norm) else None
         ev = None
         if ops.TRACE is not None:

@@ -479,16 +479,17 @@ def from_operand_image(img):
 
 
 def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual=None,
-           relu=False, l2norm=False, out=None, split_k=0, variant=0, fused_reduce=False, flags=None, staging=None,
-           operand_format=0):
+           relu=False, l2norm=False, out=None, split_k=0, variant=0, flags=None, staging=None,
+           operand_format=0, n_out_dev=None, slots_extra=0):
     """out[o] = epilogue(sum_k in[nbr[k][o]] @ W[k]) -- imf_spconv_fwd.  `operand_format` (variant 6, unsplit): FMT_A_SPLIT
     | FMT_RES_SPLIT | FMT_OUT_SPLIT -- which of in_a / in_b, residual, out are split-f16 operand images
     (`to_operand_image`) instead of fp32 rows.  `flags`: optional int32[1] device word that
     receives IMF_FLAG_RANGE (32) when an output is NaN or >= 65504 in magnitude.  `staging`: a key of STAGING_TAGS --
     None / "dma" = the library default (LDS-DMA kernel k_spconv_g), "wave*" = a workgroup shape of the wave-split kernel
     for coarse levels (csrc/spconv_w.hip; kvol > 1, cout % 64 == 0, no split-K); "regs" = variant 0's register-staged
-    k_spconv_mfma (variants 6 / 3 have none: IMF_EUNSUPPORTED / IMF_EINVAL).  `fused_reduce` (variant 0, split_k > 1):
-    the in-launch split-K combine of that kernel."""
+    k_spconv_mfma (variants 6 / 3 have none: IMF_EUNSUPPORTED / IMF_EINVAL).  `n_out_dev`: capacity mode -- int32[1]
+    device word with the actual row count; `rb`'s tables and `out` are sized for capacities, `slots_extra` = slots the map
+    lays out beyond roundup64(rows) (512 for transposed maps); the launch must be unsplit (split_k=1)."""
     _req(in_a, torch.float32, "in_a", 2)
     if in_b is not None:
         _req(in_b, torch.float32, "in_b", 2)
@@ -518,10 +519,9 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     if nbytes:
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=in_a.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-    if split > 1:
-        if fused_reduce and variant in (0, 6):
-            tk = torch.zeros(rb.n_slots // TILE_ROWS * max(1, cout // 32), dtype=torch.int32, device=in_a.device)
-            a.tickets = tk.data_ptr()
+    if n_out_dev is not None:
+        _req(n_out_dev, torch.int32, "n_out_dev", 1)
+        a.n_out_dev, a.slots_extra = n_out_dev.data_ptr(), int(slots_extra)
     big = max(in_a.numel(), 0 if in_b is None else in_b.numel()) * 4 >= 2 ** 31
     if variant in (6, 3) and big:
         raise ImfError("variants 6 / 3 address their inputs through a 2 GiB buffer window: use variant 0 for larger matrices")
@@ -539,7 +539,7 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     check(L.imf_spconv_fwd(C.byref(a), _stream()), "imf_spconv_fwd")
     if ev is not None:
         cin = a.c_a + a.c_b
-        TRACE.append(dict(kernel=conv_kernel_name(variant, cin, cout, "regs" if (staging == "regs" or fused_reduce) else staging),
+        TRACE.append(dict(kernel=conv_kernel_name(variant, cin, cout, staging),
                           kvol=rb.kvol, cin=cin, cout=cout, rb=rb, split=split, ev=ev))
     return out
 

@@ -261,7 +261,7 @@ typedef struct imf_conv_args {
   int32_t variant;        /* 0 = fp32 MFMA (v_mfma_f32_16x16x4_f32: the reference's arithmetic), since round 5 on the LDS-DMA
                                  kernels k_spconv_g / k_spconv_w (AR = kArF32) wherever their tables cover the shape
                                  (kvol <= 27, kvol * cin / 32 < 224, <= 1024 channels per source, inputs < 2 GiB), else --
-                                 or with IMF_TAG_REGS / `tickets` -- on the register-staged k_spconv_mfma;
+                                 or with IMF_TAG_REGS -- on the register-staged k_spconv_mfma;
                              1 = the same arithmetic without any pipeline (simple reference kernel; any kvol);
                              2, 4, 5 = retired round-1 experiments (their measurements: DESIGN.md 4), IMF_EINVAL;
                              3 = "bf16x3": fp32 operands carried exactly by three bf16 parts each, six
@@ -274,26 +274,18 @@ typedef struct imf_conv_args {
                                  in_a / in_b smaller than 2 GiB each: raw-buffer addressing) */
   void *workspace;        /* split-K partial sums (NULL allowed iff split_k resolves to 1) */
   size_t workspace_bytes; /* >= imf_spconv_workspace_bytes(n_slots, cout, split)                  */
-  int32_t *tickets;       /* optional: int32[n_tiles * n_slabs] arrival counters, ZERO on entry (left zero on
-                             exit): with split_k > 1 the last partition to finish a tile reduces it inside
-                             the same launch (agent-scope release/acquire) -- no second kernel.  Variant 0 only (its
-                             register-staged kernel k_spconv_mfma); variants 6 / 3 answer IMF_EUNSUPPORTED */
   void *ev_begin, *ev_end; /* optional hipEvent_t pair recorded on `stream` immediately around the
                               main MFMA kernel (not the split-K reduce): live roofline timing     */
-  /* Capacity mode (variant 6; variant 0 with split_k == 1), for launch sequences captured once and replayed on fragments of different
-   * size: n_out / n_slots (and the rulebook) are sized for a CAPACITY and the actual row count is read from
-   * device memory; tiles beyond it exit at once.  dyn_split_kvol != 0: the number of kernel-offset partitions
-   * is imf_spconv_auto_split(actual slots, cout, dyn_split_kvol) evaluated on the device -- split_k then only
-   * sizes the grid and the workspace: it must cover the largest value expected (imf_spconv_max_split covers any
-   * row count; a smaller cover raises bit 4 of *dyn_err when exceeded) -- so the result is bit-identical to an
-   * exact-size launch.  slots_extra: slots the rulebook lays out beyond roundup64(rows) (512 for
-   * imf_rulebook_transpose's parity classes, else 0). */
+  /* Capacity mode (any variant), for launch sequences captured once and replayed on fragments of different size:
+   * n_out / n_slots (and the rulebook) are sized for a CAPACITY and the actual row count is read from device
+   * memory; tiles beyond it exit at once.  A capacity-mode launch is UNSPLIT on every kernel (split_k must resolve
+   * to 1, IMF_EINVAL otherwise), so the result is bit-identical to an exact-size unsplit launch.  slots_extra:
+   * slots the rulebook lays out beyond roundup64(rows) (512 for imf_rulebook_transpose's parity classes, else 0). */
   const int32_t *n_out_dev;
-  int32_t dyn_split_kvol, slots_extra;
+  int32_t slots_extra;
   int32_t kernel_tag;     /* variants 6, 3 and 0: IMF_TAG_* bits (below) -- which kernel and workgroup shape; 0 = k_spconv_g */
-  int32_t *dyn_err;       /* optional device flag word (any mode): IMF_FLAG_SPLIT_COVER when the rule asks for more
-                             partitions than split_k covers; IMF_FLAG_RANGE when an OUTPUT value is NaN or |y| >= 65504,
-                             i.e. cannot be an operand of a following variant-6 convolution */
+  int32_t *dyn_err;       /* optional device flag word (any mode): IMF_FLAG_RANGE when an OUTPUT value is NaN or
+                             |y| >= 65504, i.e. cannot be an operand of a following variant-6 convolution */
   int32_t geglu;          /* variant 6, kvol == 1, cout % 64 == 0, unsplit, no scale / residual / relu / l2norm: GEGLU
                              epilogue of the fusion block's feed-forward (model/attention_fusion.py:20-23,56-63).  The
                              weight image's columns are arranged per 64-column slab y as [32 values | 32 gates] of hidden
@@ -315,14 +307,14 @@ typedef struct imf_conv_args {
  * count and the unit shape only, never on the row count: exact and capacity mode agree bit for bit. */
 #define IMF_TAG_LABEL   1   /* profiling label: the identical kernel under a second symbol (k_spconv_g<.., 1>, whole-tile
                                k_spconv_w of 8 wavefronts: the image branch's dense convolutions) */
-#define IMF_TAG_REGS    2   /* variant 0: the register-staged fp32 kernel k_spconv_mfma (also taken with `tickets`; the one
-                               that serves inputs beyond the 2 GiB buffer window); variants 6 / 3: IMF_EUNSUPPORTED */
+#define IMF_TAG_REGS    2   /* variant 0: the register-staged fp32 kernel k_spconv_mfma (the one that serves inputs beyond
+                               the 2 GiB buffer window); variants 6 / 3: IMF_EUNSUPPORTED / IMF_EINVAL */
 #define IMF_TAG_WAVE8   4   /* the wave-split kernel k_spconv_w (csrc/spconv_w.hip) with 8 wavefronts per workgroup ... */
 #define IMF_TAG_WAVE4   8   /* ... or with 4 (WAVE8 wins when both are set) -- for levels of a few hundred 64-row tiles or
                                fewer: one workgroup owns a (unit of rows, 64-column slab) for all kernel offsets, its
                                wavefronts split the (offset, 32-channel chunk) list into contiguous ranges and combine
                                their partial tiles through LDS in wavefront order, epilogue in the same launch.  Needs
-                               cout % 64 == 0, kvol > 1 or cin >= 256, split_k <= 1, no tickets */
+                               cout % 64 == 0, kvol > 1 or cin >= 256, split_k <= 1 */
 #define IMF_TAG_HEAD   16   /* trace label of the fused pointwise head (imf_net_trace.kernel_tag only; not a launch shape) */
 #define IMF_TAG_HALF   64   /* with WAVE4, variant 3 (with OCC also WAVE8): HALF-TILE workgroups -- 32 of a tile's 64 rows
                                each, same offset list and per-row sums: twice the workgroups for levels that leave CUs idle */
@@ -339,12 +331,13 @@ typedef struct imf_conv_args {
 
 /* Flag bits the kernels OR into a caller-provided device word (imf_conv_args.dyn_err, imf_resunet_io.flags, meta[1]
  * of the capacity mode).  A flagged result must not be used: redo the fragment (larger capacities / exact mode for
- * 2..16; the fp32-MFMA variant 0 for IMF_FLAG_RANGE). */
+ * 2..8; the fp32-MFMA variant 0 for IMF_FLAG_RANGE).  Bit 16 is RETIRED and not to be reused: recorded flag words carry
+ * it (it said that a capacity-mode launch had fewer rows than its device-side split-K rule covered; no kernel raises it
+ * since version 101). */
 #define IMF_FLAG_COORD_RANGE  1   /* a point fell outside [-2^17, 2^17) voxels or was NaN */
 #define IMF_FLAG_CAPACITY     2   /* a pyramid level exceeded its row capacity */
 #define IMF_FLAG_BITGRID      4   /* level-0 bounding box larger than the conv1 bit grid */
 #define IMF_FLAG_EMPTY_ITEM   8   /* a batch item without voxels */
-#define IMF_FLAG_SPLIT_COVER 16   /* fewer rows than a quarter of the capacity */
 #define IMF_FLAG_RANGE       32   /* an activation left the f16 range of the split-f16 convolution operands */
 
 /* Kernel-offset partitions imf_spconv_fwd will use for this shape when args.split_k == 0: small
@@ -352,9 +345,6 @@ typedef struct imf_conv_args {
  * partial sums are combined -- in a fixed order, hence still bit-reproducible -- by a second
  * kernel that also applies the epilogue. */
 int imf_spconv_auto_split(int64_t n_slots, int cout, int kvol);
-int imf_spconv_max_split(int cout, int kvol);   /* largest value the rule returns for any row count */
-/* Tuning aid: resident workgroups per CU reported by the runtime for kernel `variant`. */
-int imf_spconv_occupancy(int variant, int co_blk, int j);
 size_t imf_spconv_workspace_bytes(int64_t n_slots, int cout, int split);
 
 /* Replaces: ME.MinkowskiConvolution / ME.MinkowskiConvolutionTranspose forward

@@ -89,6 +89,49 @@ def test_arena_sizes_equal_the_recorded_ones():
         assert g == w, f"{w['desc']} n={w['n']}: {g} != recorded {w}"
 
 
+def test_arena_sizes_of_the_fixture_fragment_without_a_conv_workspace(clouds):
+    """The executor's layout no longer names a convolution workspace (every launch is unsplit; the workspace was the slack
+    of the float arena, nothing was reserved for it), so the four totals must not move.  Row counts: the fixture fragment's
+    four levels at 5 cm and at 2.5 cm (recomputed here by the oracle); byte counts: what the library of the commit BEFORE
+    that change returned for them (the model the tests run, conv1 k5; bounding box and bit-grid words of gen_arena_bytes)."""
+    import ctypes
+    import importlib.util
+    from imfnet_amd import _lib
+    recorded = {(5182, 1453, 413, 112): dict(int_exact=2851376, int_exact_bbox=3233296, float_exact=11945728,
+                                             int_cap={"4": 2851392, "262144": 3899952}, float_cap=11945728),
+                (18977, 5182, 1453, 413): dict(int_exact=9815504, int_exact_bbox=10197424, float_exact=43374336,
+                                               int_cap={"4": 9815520, "262144": 10864080}, float_cap=43374336)}
+    rows = []
+    for vs in (0.05, 0.025):
+        c = O.voxelize(clouds[0].astype(np.float64), vs)[0]
+        rows.append((len(c),) + tuple(len(O.downsample(c, s)[0]) for s in (2, 4, 8)))
+    assert rows == list(recorded)
+    spec = importlib.util.spec_from_file_location("gen_arena_bytes", os.path.join(GOLDEN, "gen_arena_bytes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    gen.ROWS = rows                                    # (this module instance is the test's own)
+    got = [e for e in gen.sizes(ctypes.CDLL(_lib.LIB_PATH)) if e["desc"] == "bn2c_k5"]
+    assert [dict(desc="bn2c_k5", n=list(r), **recorded[r]) for r in rows] == got
+
+
+def test_capacity_mode_launch_refuses_a_split():
+    """imf_spconv_fwd validates on the host before it launches anything: a launch with n_out_dev (capacity mode) is unsplit
+    on every kernel family -- split_k = 2 answers IMF_EINVAL with a message that names capacity mode, whatever the variant
+    (the pointers are never dereferenced: the call returns before the launch)."""
+    import ctypes
+    from imfnet_amd import _lib
+    L = _lib.lib()
+    for variant in (0, 3, 6):                                     # (1, the kernel without a pipeline, is never split)
+        for split_k, kvol in ((2, 27), (0, 27), (5, 8)):         # 0: the automatic rule gives 8 for 17 tiles x 1 slab
+            a = _lib.ConvArgs()
+            a.in_a = a.w_packed = a.out = a.nbr = a.tile_mask = a.tile_rows = a.workspace = a.n_out_dev = 256
+            a.c_a, a.cout, a.kvol, a.n_slots, a.n_out = 64, 64, kvol, 1088, 1030
+            a.split_k, a.variant, a.workspace_bytes = split_k, variant, 1 << 30
+            assert L.imf_spconv_fwd(ctypes.byref(a), None) == -1, (variant, split_k)       # IMF_EINVAL
+            msg = L.imf_last_error().decode()
+            assert "capacity mode" in msg and "unsplit" in msg, msg
+
+
 def test_kernel_tag_names_mirror_the_header():
     """The IMF_TAG_* constants of include/imfnet_hip.h, their mirror in _lib and the staging table of ops: the values are
     part of the ABI (bench.py reads 64 and 128 from trace records, C callers pass integers), so they are pinned here."""

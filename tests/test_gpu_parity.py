@@ -158,7 +158,7 @@ def _rb_and_ref(cm, g, which):
     return cm.conv_rulebook(1, 1, 1), None, len(g.levels[0])
 
 
-@pytest.mark.parametrize("mode", ["auto", "split1", "split5", "split5_fused", "simple", "f32_regs", "f32_regs_split5",
+@pytest.mark.parametrize("mode", ["auto", "split1", "split5", "simple", "f32_regs", "f32_regs_split5",
                                   "f32_wave8", "f32_wave4", "b3", "b3_split1", "b3_split5", "b3_wave8", "b3_wave4", "b3_wave4h", "b3_wave8u", "b3_wave4u", "b3_wave4o", "b3_wave4h4", "b3_wave8h4",
                                   "h3", "h3_split1", "h3_split5", "h3_wave8", "h3_wave4"])
 @pytest.mark.parametrize("ca,cb,cout,which", CONV_CASES)
@@ -171,10 +171,9 @@ def test_spconv_matches_oracle(ops, geom_s5, ca, cb, cout, which, mode):
     fa, fb = _rand((n_in, ca), 10), (_rand((n_in, cb), 11) if cb else None)
     w = _rand((kvol, ca + cb, cout), 12, 1.0 / np.sqrt(kvol * (ca + cb)))
     # variant 0 (fp32 MFMA, the reference's arithmetic) runs on the LDS-DMA kernels since round 5 (AR = kArF32): "auto" /
-    # "split1" / "split5" = k_spconv_g, "f32_wave8" / "f32_wave4" = k_spconv_w; "f32_regs*" / "split5_fused" = round 1's
-    # register-staged k_spconv_mfma (kernel_tag bit 1, or the in-launch combine it alone implements)
+    # "split1" / "split5" = k_spconv_g, "f32_wave8" / "f32_wave4" = k_spconv_w; "f32_regs*" = round 1's
+    # register-staged k_spconv_mfma (kernel_tag bit 1)
     kw = {"auto": {}, "split1": {"split_k": 1}, "split5": {"split_k": 5}, "simple": {"variant": 1},
-          "split5_fused": {"split_k": 5, "fused_reduce": True},
           "f32_regs": {"staging": "regs"}, "f32_regs_split5": {"staging": "regs", "split_k": 5},
           "f32_wave8": {"staging": "wave8"}, "f32_wave4": {"staging": "wave4"},
           # variant 3 = bf16x3: fp32 operands as three bf16 parts each (exact), six bf16 MFMAs per 32 channels
@@ -192,7 +191,7 @@ def test_spconv_matches_oracle(ops, geom_s5, ca, cb, cout, which, mode):
           "h3_wave8": {"variant": 6, "staging": "wave8"}, "h3_wave4": {"variant": 6, "staging": "wave4"}}[mode]
     if mode.endswith(("wave8", "wave4", "wave4h", "wave8u", "wave4u", "wave4o", "wave4h4", "wave8h4")) and (kvol == 1 or cout % 64):
         pytest.skip("the wave-split kernel covers kvol > 1 and cout % 64 == 0")
-    if mode in ("split5", "split5_fused", "h3_split5", "f32_regs_split5", "b3_split5") and kvol == 1:
+    if mode in ("split5", "h3_split5", "f32_regs_split5", "b3_split5") and kvol == 1:
         pytest.skip("pointwise convolution has a single offset")
     out = ops.spconv(fa.to(DEV), ops.pack_weights(w.to(DEV), variant=kw.get("variant", 0)), cout, rb,
                      in_b=None if fb is None else fb.to(DEV), **kw).cpu()
@@ -615,10 +614,39 @@ def test_spconv_deterministic(ops, geom_s5):
         a = ops.spconv(f, wp, 64, rb, **kw)
         b = ops.spconv(f, wp, 64, rb, **kw)
         assert torch.equal(a, b)
-    # in-kernel combine == two-pass combine, bit for bit, and stable over many launches
-    ref = ops.spconv(f, wp, 64, rb, split_k=6, fused_reduce=False)
-    for _ in range(20):
-        assert torch.equal(ops.spconv(f, wp, 64, rb, split_k=6, fused_reduce=True), ref)
+
+
+@pytest.mark.parametrize("variant", [0, 3, 6])
+def test_spconv_capacity_launch_is_the_exact_unsplit_one(ops, geom_s5, variant):
+    """imf_spconv_fwd in capacity mode (n_out_dev): tables and output sized for roundup64(rows) + 128 spare rows, the
+    device word holds the true row count -- 5182 rows: a partly filled last tile and two whole padding tiles.  The first
+    rows equal the exact-size unsplit launch bit for bit; the spare rows of a NaN-prefilled output stay NaN although the
+    padding tiles' tables are decoys that point at them (all offsets active, input row 0): the kernels leave those tiles by
+    the device-side row count alone.  The stride-1 map and the transposed map (512 extra slots), 32 -> 32 and 64 + 64 -> 64.
+    A capacity launch is unsplit on every kernel: a split is refused."""
+    from imfnet_amd import ImfError
+    cm, g = geom_s5
+    for rb, n_in, extra in ((cm.conv_rulebook(1, 3, 1), len(g.levels[0]), 0),
+                            (cm.transpose_rulebook(2, 3, 2), len(g.levels[1]), 512)):
+        n, K, S = rb.n_out, rb.kvol, rb.n_slots
+        cap = (n + 63) // 64 * 64 + 128
+        assert n == 5182 and S == cap - 128 + extra
+        spare = torch.arange(n, n + 128, dtype=torch.int32, device=DEV)
+        tile_rows = torch.cat([rb.tile_rows, spare])
+        nbr = torch.cat([rb.nbr.view(K, S), torch.zeros((K, 128), dtype=torch.int32, device=DEV)], 1).contiguous().view(-1)
+        mask = torch.cat([rb.tile_mask, torch.tensor([(1 << K) - 1, 0, 0, 0] * 2, dtype=torch.int32, device=DEV)])
+        rb_cap = ops.Rulebook(tile_rows, nbr, mask, S + 128, cap, K, rb.max_active)
+        word = torch.tensor([n], dtype=torch.int32, device=DEV)
+        for ca, cb, cout in ((32, 0, 32), (64, 64, 64)):
+            fa, fb = _rand((n_in, ca), 70).to(DEV), (_rand((n_in, cb), 71).to(DEV) if cb else None)
+            wp = ops.pack_weights(_rand((K, ca + cb, cout), 72, 0.05).to(DEV), variant=variant)
+            exact = ops.spconv(fa, wp, cout, rb, in_b=fb, split_k=1, variant=variant)
+            out = torch.full((cap, cout), float("nan"), device=DEV)
+            ops.spconv(fa, wp, cout, rb_cap, in_b=fb, split_k=1, variant=variant, out=out, n_out_dev=word, slots_extra=extra)
+            assert torch.equal(out[:n], exact) and not torch.isnan(exact).any()
+            assert torch.isnan(out[n:]).all()
+            with pytest.raises(ImfError, match="capacity mode"):
+                ops.spconv(fa, wp, cout, rb_cap, in_b=fb, split_k=2, variant=variant, out=out, n_out_dev=word, slots_extra=extra)
 
 
 @pytest.mark.parametrize("cin,cout,ks", [(1, 32, 5), (1, 32, 3), (3, 32, 3), (4, 64, 3)])
@@ -687,9 +715,8 @@ def test_spconv_argument_errors(ops, geom_s5):
         with pytest.raises(ImfError):
             ops.spconv(f[:, :32].contiguous(), wp, 32, rb, variant=retired)
     wp6 = ops.pack_weights(torch.zeros(27, 32, 32, device=DEV), split16=True)
-    for kw in ({"staging": "regs"}, {"split_k": 4, "fused_reduce": True}):      # variant 6 has neither: IMF_EUNSUPPORTED
-        with pytest.raises(ImfError, match="variant 6 has no register-staged kernel"):
-            ops.spconv(f[:, :32].contiguous(), wp6, 32, rb, variant=6, **kw)
+    with pytest.raises(ImfError, match="variant 6 has no register-staged kernel"):    # IMF_EUNSUPPORTED
+        ops.spconv(f[:, :32].contiguous(), wp6, 32, rb, variant=6, staging="regs")
 
 
 # ------------------------------------------------------------------ whole model
