@@ -381,68 +381,73 @@ __device__ __forceinline__ int parity_class(int4 c, int ts) {
 }
 
 // Parity-class grouping of the transposed rulebook, DETERMINISTIC: a row's slot is
-//   class base + (rows of its class in earlier blocks) + (its rank among its class inside the block),
-// all three order-defined (no arrival-order atomics), so the slot table -- and with it the split-K
-// partition a row falls into -- is the same on every run.  blockcnt: [n_blocks][8] scratch (the head of
-// the not-yet-written neighbour table).
-__global__ void __launch_bounds__(256)
-k_class_count(const int32_t *__restrict__ coords, int64_t n, const int32_t *__restrict__ n_dev, int ts,
-              int32_t *__restrict__ blockcnt) {
-  __shared__ int cnt[8];
-  if (n_dev) n = min((int64_t)*n_dev, n);
-  if (threadIdx.x < 8) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) atomicAdd(&cnt[parity_class(reinterpret_cast<const int4 *>(coords)[i], ts)], 1);   // a count: order-free
-  __syncthreads();
-  if (threadIdx.x < 8) blockcnt[blockIdx.x * 8 + threadIdx.x] = cnt[threadIdx.x];
-}
-
-// one workgroup: per class, exclusive scan of the block counts (in place) and the tile-aligned class bases
-__global__ void __launch_bounds__(256)
-k_class_bases(int32_t *__restrict__ blockcnt, int nb, int32_t *__restrict__ counters) {
-  __shared__ int part[8][32], total[8];
-  const int p = threadIdx.x >> 5, t = threadIdx.x & 31;       // 8 classes x 32 threads
-  const int per = (nb + 31) / 32;
-  const int lo = min(nb, t * per), hi = min(nb, lo + per);
-  int s = 0;
-  for (int b = lo; b < hi; ++b) s += blockcnt[b * 8 + p];
-  part[p][t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int q = 0; q < 32; ++q) {
-      const int v = part[p][q];
-      part[p][q] = run;
-      run += v;
-    }
-    total[p] = run;
-  }
-  __syncthreads();
-  int run = part[p][t];
-  for (int b = lo; b < hi; ++b) {
-    const int v = blockcnt[b * 8 + p];
-    blockcnt[b * 8 + p] = run;
-    run += v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int base = 0;
-    for (int q = 0; q < 8; ++q) {
-      counters[q] = total[q];
-      counters[8 + q] = base;
-      base += (total[q] + IMF_TILE_ROWS - 1) / IMF_TILE_ROWS * IMF_TILE_ROWS;
-    }
-  }
-}
+//   class base + (rows of its class in earlier chunks) + (its rank among its class inside its chunk of 256 rows),
+// all three order-defined (no arrival-order atomics), so the slot table is the same on every run.
+//
+// No scan launch between count and assign, and no state between calls.  k_class_count leaves per-chunk counts cnt[nb][8] and
+// per-group sums grp[ng][8] (a group = cpg consecutive chunks, counted by one workgroup; ng <= kClassGroups) in the head of
+// the not-yet-written neighbour table.  k_class_assign then forms what it needs itself: every workgroup adds up the <= 256
+// group sums (class totals -> the tile-aligned class bases; groups ahead of its own) and the < cpg chunks ahead of it inside
+// its group -- O(ng + cpg) coalesced L2 reads per workgroup instead of the one-workgroup scan launch that stood between
+// the two (k_class_bases: 4.6 - 11 us, serial).  Integer sums: the table equals the scan's bit for bit.  No workgroup waits
+// for another, and nothing (no ticket, no counter) has to be zero on entry: `counters` is uninitialised scratch in the C
+// ABI, and a ticket word in the module would be shared by the maps that two streams build at the same time.
+constexpr int kClassGroups = 256;
 
 __global__ void __launch_bounds__(256)
-k_class_assign(const int32_t *__restrict__ coords, int64_t n, const int32_t *__restrict__ n_dev, int ts,
-               const int32_t *__restrict__ counters, const int32_t *__restrict__ blockbase,
-               int32_t *__restrict__ tile_rows) {
+k_class_count(const int32_t *__restrict__ coords, int64_t n, const int32_t *__restrict__ n_dev, int ts, int nb, int cpg,
+              int32_t *__restrict__ cnt, int32_t *__restrict__ grp) {
   __shared__ int wcnt[4][8];
+  const int c0 = blockIdx.x * cpg, c1 = min(nb, c0 + cpg);      // this workgroup's chunks (grid = ng: c0 < nb)
   if (n_dev) n = min((int64_t)*n_dev, n);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int sum = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int64_t row = (int64_t)c * 256 + threadIdx.x;
+    const int p = (row < n) ? parity_class(reinterpret_cast<const int4 *>(coords)[row], ts) : -1;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const unsigned long long bal = __ballot(p == q);
+      if (lane == 0) wcnt[w][q] = __popcll(bal);
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+      const int v = wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
+      cnt[c * 8 + threadIdx.x] = v;
+      sum += v;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 8) grp[blockIdx.x * 8 + threadIdx.x] = sum;
+}
+
+__global__ void __launch_bounds__(256)
+k_class_assign(const int32_t *__restrict__ coords, int64_t n, const int32_t *__restrict__ n_dev, int ts, int cpg, int ng,
+               const int32_t *__restrict__ cnt, const int32_t *__restrict__ grp, int32_t *__restrict__ counters,
+               int32_t *__restrict__ tile_rows) {
+  __shared__ int wcnt[4][8], wtot[4][8], wpre[4][8];
+  if (n_dev) n = min((int64_t)*n_dev, n);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  // class totals and the rows of each class ahead of this chunk: thread = (class q, 1 of 32 strides), class fastest
+  {
+    const int q = threadIdx.x & 7, t = threadIdx.x >> 3, gme = blockIdx.x / cpg;
+    int tot = 0, pre = 0;
+    for (int g = t; g < ng; g += 32) {
+      const int v = grp[g * 8 + q];
+      tot += v;
+      if (g < gme) pre += v;
+    }
+    for (int c = gme * cpg + t; c < (int)blockIdx.x; c += 32) pre += cnt[c * 8 + q];
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+      tot += __shfl_xor(tot, o, 64);
+      pre += __shfl_xor(pre, o, 64);
+    }
+    if (lane < 8) {
+      wtot[w][lane] = tot;
+      wpre[w][lane] = pre;
+    }
+  }
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int p = (i < n) ? parity_class(reinterpret_cast<const int4 *>(coords)[i], ts) : -1;
   int local = 0;
@@ -453,18 +458,25 @@ k_class_assign(const int32_t *__restrict__ coords, int64_t n, const int32_t *__r
     if (lane == 0) wcnt[w][q] = __popcll(bal);
   }
   __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x < 8) {   // counters[0..7]: rows per class, [8..15]: the tile-aligned class bases
+    int base = 0;
+    for (int q = 0; q < (int)threadIdx.x; ++q)
+      base += (wtot[0][q] + wtot[1][q] + wtot[2][q] + wtot[3][q] + IMF_TILE_ROWS - 1) / IMF_TILE_ROWS * IMF_TILE_ROWS;
+    counters[threadIdx.x] = wtot[0][threadIdx.x] + wtot[1][threadIdx.x] + wtot[2][threadIdx.x] + wtot[3][threadIdx.x];
+    counters[8 + threadIdx.x] = base;
+  }
   if (p >= 0) {
-    int off = counters[8 + p] + blockbase[blockIdx.x * 8 + p] + local;
+    int off = wpre[0][p] + wpre[1][p] + wpre[2][p] + wpre[3][p] + local;
+    for (int q = 0; q < p; ++q)
+      off += (wtot[0][q] + wtot[1][q] + wtot[2][q] + wtot[3][q] + IMF_TILE_ROWS - 1) / IMF_TILE_ROWS * IMF_TILE_ROWS;
     for (int v = 0; v < w; ++v) off += wcnt[v][p];
     tile_rows[off] = (int32_t)i;
   }
 }
 
 __global__ void __launch_bounds__(256)
-k_init_transpose(int32_t *counters, int32_t *tile_rows, int64_t n_slots, uint32_t *tile_mask,
-                 int64_t n_mask) {
+k_init_transpose(int32_t *tile_rows, int64_t n_slots, uint32_t *tile_mask, int64_t n_mask) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 16) counters[i] = 0;
   if (i < n_slots) tile_rows[i] = -1;
   if (i < n_mask) tile_mask[i] = 0u;
 }
@@ -845,13 +857,14 @@ static int rulebook_transpose_impl(const imf_slot *coarse_table, int64_t coarse_
   IMF_REQUIRE((coarse_capacity & (coarse_capacity - 1)) == 0, "capacity not a power of 2");
   hipStream_t st = (hipStream_t)stream;
   const int kvol = 27;
-  k_init_transpose<<<(unsigned)div_up(n_slots, 256), 256, 0, st>>>(
-      counters, tile_rows, n_slots, tile_mask, n_slots / IMF_TILE_ROWS * IMF_MASK_WORDS);
-  const unsigned nb = (unsigned)div_up(n_fine, 256);
-  int32_t *blockcnt = nbr;   // scratch: the neighbour table is written by k_rulebook below (nb*8 <= 27*n_slots)
-  k_class_count<<<nb, 256, 0, st>>>(fine_coords, n_fine, n_fine_dev, ts_fine, blockcnt);
-  k_class_bases<<<1, 256, 0, st>>>(blockcnt, (int)nb, counters);
-  k_class_assign<<<nb, 256, 0, st>>>(fine_coords, n_fine, n_fine_dev, ts_fine, counters, blockcnt, tile_rows);
+  const int nb = (int)div_up(n_fine, 256);                      // chunks of 256 fine rows
+  const int cpg = (int)div_up(nb, kClassGroups), ng = (int)div_up(nb, cpg);
+  // scratch: the neighbour table is written by k_rulebook below ((nb + ng) * 8 <= 16 nb words < 27 n_slots)
+  int32_t *cnt = nbr, *grp = nbr + (size_t)nb * 8;
+  k_init_transpose<<<(unsigned)div_up(n_slots, 256), 256, 0, st>>>(tile_rows, n_slots, tile_mask,
+                                                                  n_slots / IMF_TILE_ROWS * IMF_MASK_WORDS);
+  k_class_count<<<(unsigned)ng, 256, 0, st>>>(fine_coords, n_fine, n_fine_dev, ts_fine, nb, cpg, cnt, grp);
+  k_class_assign<<<(unsigned)nb, 256, 0, st>>>(fine_coords, n_fine, n_fine_dev, ts_fine, cpg, ng, cnt, grp, counters, tile_rows);
   k_rulebook<-1, true><<<(unsigned)(n_slots / IMF_TILE_ROWS), 256, 0, st>>>(
       coarse_table, (uint32_t)(coarse_capacity - 1), fine_coords, n_fine, n_fine_dev, ts_fine, ksize,
       kvol, tile_rows, nbr, tile_mask, n_slots);

@@ -21,6 +21,16 @@ __device__ __forceinline__ void kernel_offset(int k, int ksize, int &dx, int &dy
 //     memset launch ahead of the kernel (round 3; the (slot, k)-thread kernel before it: 47 us for the level-0 3x3x3 map
 //     of the pair + a 4 us memset, on the critical path since conv1 got shorter than it).
 // SIGN = +1: in = out + off*ts (conv); SIGN = -1: coarse = fine - off*ts (transposed conv).
+//
+// Transposed maps probe the coarse LATTICE only.  The coarse table holds multiples of 2 ts, so fine - off*ts can be in it
+// only if it is one on every axis: 1, 2, 4 or 8 of the 27 offsets of a row, by its parity class (3.4 on average).  Every
+// other (row, offset) is -1 without a key, a hash or a table load (the parent probed them all: 87 % of its loads).  The
+// tiles of a transposed map hold ONE class (k_class_assign: tile-aligned class bases), so the test is made once per
+// (tile, offset) on the coordinates of the tile's first row and the whole wavefront skips the probe; -1 is still stored and
+// the mask bit stays clear.  The generic path tests per lane.
+__device__ __forceinline__ bool on_coarse_lattice(int x, int y, int z, int ts) {
+  return ((x | y | z) & (2 * ts - 1)) == 0;          // ts is a power of two; two's complement: right for negatives
+}
 template <int SIGN, bool INDIRECT>
 __device__ __forceinline__ void rulebook_tile(const imf_slot *__restrict__ tab, uint32_t capmask,
                                               const int32_t *__restrict__ out_coords, int64_t n_out,
@@ -46,6 +56,14 @@ __device__ __forceinline__ void rulebook_tile(const imf_slot *__restrict__ tab, 
   if (!(empty_tile && n_out_dev)) {   // (exact-size tables: padding tiles are written as 'no input' too)
     int4 c = make_int4(0, 0, 0, 0);
     if (row >= 0) c = reinterpret_cast<const int4 *>(out_coords)[row];
+    [[maybe_unused]] int ux = 0, uy = 0, uz = 0;       // transposed, one class per tile: the tile's first row stands for all
+    if constexpr (SIGN < 0 && INDIRECT) {
+      const unsigned long long rows = __ballot(row >= 0);
+      const int first = rows ? __builtin_ctzll(rows) : 0;
+      ux = __builtin_amdgcn_readlane(c.y, first);
+      uy = __builtin_amdgcn_readlane(c.z, first);
+      uz = __builtin_amdgcn_readlane(c.w, first);
+    }
     if (kvol <= 28) {
       // 3x3x3 (and 1x1x1): the thread's <= 7 offsets as two phases -- every first-slot load issued before any is
       // looked at (one 16-byte slot = key + row), then the rare collisions walk on
@@ -53,23 +71,37 @@ __device__ __forceinline__ void rulebook_tile(const imf_slot *__restrict__ tab, 
       uint64_t want[KPT];
       uint32_t hs[KPT];
       uint4 got[KPT];
+      [[maybe_unused]] bool probe[KPT];                // transposed: (tile, offset) on the coarse lattice -- wavefront-uniform
 #pragma unroll
       for (int j = 0; j < KPT; ++j) {
         const int k = g + 4 * j;
         want[j] = kEmptyKey;                           // "no probe": resolves to -1 below
         hs[j] = 0;
+        if constexpr (SIGN < 0 && INDIRECT) {
+          int dx, dy, dz;
+          kernel_offset(k < kvol ? k : 0, ksize, dx, dy, dz);
+          probe[j] = k < kvol && on_coarse_lattice(ux - dx * ts, uy - dy * ts, uz - dz * ts, ts);
+          if (!probe[j]) continue;
+        }
         if (k < kvol && row >= 0) {
           int dx, dy, dz;
           kernel_offset(k, ksize, dx, dy, dz);
           const int x = c.y + SIGN * dx * ts, y = c.z + SIGN * dy * ts, z = c.w + SIGN * dz * ts;
-          if (coord_in_range(x, y, z)) {
+          bool probed = coord_in_range(x, y, z);
+          if constexpr (SIGN < 0 && !INDIRECT) probed = probed && on_coarse_lattice(x, y, z, ts);
+          if (probed) {
             want[j] = pack_key(c.x, x, y, z);
             hs[j] = hash_slot(want[j], tshift, capmask);
           }
         }
       }
 #pragma unroll
-      for (int j = 0; j < KPT; ++j) got[j] = *reinterpret_cast<const uint4 *>(tab + hs[j]);
+      for (int j = 0; j < KPT; ++j) {
+        if constexpr (SIGN < 0 && INDIRECT) {
+          if (!probe[j]) continue;                     // (got[j] stays unread: want[j] is kEmptyKey)
+        }
+        got[j] = *reinterpret_cast<const uint4 *>(tab + hs[j]);
+      }
 #pragma unroll
       for (int j = 0; j < KPT; ++j) {
         const int k = g + 4 * j;
@@ -90,7 +122,9 @@ __device__ __forceinline__ void rulebook_tile(const imf_slot *__restrict__ tab, 
           int dx, dy, dz;
           kernel_offset(k, ksize, dx, dy, dz);
           const int x = c.y + SIGN * dx * ts, y = c.z + SIGN * dy * ts, z = c.w + SIGN * dz * ts;
-          if (coord_in_range(x, y, z)) found = hash_find(tab, capmask, pack_key(c.x, x, y, z), tshift);
+          bool probed = coord_in_range(x, y, z);
+          if constexpr (SIGN < 0) probed = probed && on_coarse_lattice(x, y, z, ts);
+          if (probed) found = hash_find(tab, capmask, pack_key(c.x, x, y, z), tshift);
         }
         nbr[(int64_t)k * n_slots + slot] = found;
         if (__ballot(found >= 0) != 0ull) m[k >> 5] |= 1u << (k & 31);
