@@ -92,6 +92,20 @@ class ImageDesc(C.Structure):
                 ("variant", C.c_int32)]
 
 
+class ImageTable(C.Structure):
+    """struct imf_image_table."""
+    _fields_ = [("tile_rows", C.c_void_p), ("nbr", C.c_void_p), ("tile_mask", C.c_void_p), ("n_slots", C.c_int64),
+                ("n_out", C.c_int64), ("kvol", C.c_int32)]
+
+
+IMAGE_TRAIN_TABLES = ("t4", "t48", "t48T", "td", "tdT", "t8")
+
+
+class ImageTrainTables(C.Structure):
+    """struct imf_image_train_tables."""
+    _fields_ = [(n, ImageTable) for n in IMAGE_TRAIN_TABLES]
+
+
 class NetTrace(C.Structure):
     """struct imf_net_trace."""
     _fields_ = [("ev_begin", C.c_void_p), ("ev_end", C.c_void_p), ("nbr", C.c_void_p), ("kvol", C.c_int32),
@@ -303,6 +317,11 @@ SIGNATURES = {
     "imf_image_tokens": (_I, [_I, _I]),
     "imf_image_tables_build": (_I, [_I, _I, _I, _P, _Z, _P]),
     "imf_image_branch": (_I, [C.POINTER(ImageDesc), _P, _I, _I, _I, _P, _Z, _P, _P, _P, _I, _P, _P]),
+    "imf_image_train_tables_bytes": (_Z, [_I, _I, _I]),
+    "imf_image_train_tables_build": (_I, [_I, _I, _I, _P, _Z, C.POINTER(ImageTrainTables), _P]),
+    "imf_image_im2col7": (_I, [_P, _I, _I, _I, _P, _P]),
+    "imf_image_maxpool_forward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "imf_image_maxpool_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "imf_conv_first_bitgrid_flags": (_I, [_P, _L, _P, _I, _P, _Z, _P, _I, _P, _P, _I, _P, _P, _P]),
     "imf_fusion_attention_batched_flags": (_I, [_P, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p), _I, _I, C.POINTER(FusionWeights), C.c_float, _P, _P,

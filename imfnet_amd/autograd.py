@@ -24,6 +24,10 @@ train.loss.hardest_contrastive_loss decides when it runs.
 "hip"): every batch item in one forward and one backward call over a device-side partition of the rows;
 ResUNet2.transformer decides when it runs.
 
+`DenseConvFunction` / `MaxPoolRowsFunction` are the image encoder's convolutions and max pool on NHWC rows
+(csrc/image_train.hip, ops.TRAIN_IMAGE == "hip"): the same three kernels as `SparseConvFunction` over static pixel tables,
+`SparseBatchNormFunction` between them; model.image_encoder.ImageEncoder decides when they run.
+
 Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
 two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
 range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
@@ -118,6 +122,77 @@ class SparseConvFunction(torch.autograd.Function):
             dw = spconv_wgrad(feat, g, rb, K)
             grad_kernel = dw if kernel.dim() == 3 else dw[0]
         return grad_feat, grad_kernel, None, None
+
+
+def _dense_staging(kvol, cout):
+    """The launch shape of a dense convolution: the 8-wavefront wave-split kernel imf_image_branch runs its 3x3 layers on,
+    the library default (one unsplit k_spconv_g launch) for the pointwise ones.  Static per layer, never a function of the
+    batch or image size: the workgroup shape and a split over the taps are part of the summation order."""
+    return "wave8" if kvol == 9 and cout % 64 == 0 else None
+
+
+class DenseConvFunction(torch.autograd.Function):
+    """out [rb.n_out, co] = the dense convolution `weight` (torch layout [co, ci, kh, kw], no bias) of the NHWC rows
+    `feat` [n_in, ci] over the static pixel table `rb` (ops.ImageTrainTables; kh * kw == rb.kvol).
+      d feat    imf_spconv_fwd over `rb_opposite` (rows = the input pixels) with W[k]^T, the taps flipped (k -> K-1-k) when
+                `flip` (stride 1: the table is its own opposite); skipped when feat needs no gradient (the stem's im2col)
+      d weight  imf_spconv_wgrad over `rb`, permuted back to the parameter's layout."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, rb, rb_opposite, flip):
+        co, ci, kh, kw = weight.shape
+        if kh * kw != rb.kvol or feat.shape[1] != ci:
+            raise ImfError(f"DenseConvFunction: weight {tuple(weight.shape)} on a {rb.kvol}-tap table over {feat.shape[1]} channels")
+        feat_c = feat.detach().contiguous()
+        k3 = weight.detach().float().permute(2, 3, 1, 0).reshape(rb.kvol, ci, co).contiguous()
+        variant = training_variant(rb.kvol)
+        out = ops.spconv(feat_c, ops.pack_weights(k3, variant=variant), co, rb, variant=variant, split_k=1,
+                         staging=_dense_staging(rb.kvol, co))
+        ctx.save_for_backward(feat_c, weight)
+        ctx.rb, ctx.rb_opposite, ctx.flip = rb, rb_opposite, bool(flip)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feat, weight = ctx.saved_tensors
+        rb, rbt = ctx.rb, ctx.rb_opposite
+        co, ci, kh, kw = weight.shape
+        g = grad_out.contiguous().float()
+        grad_feat = grad_weight = None
+        if ctx.needs_input_grad[0]:
+            if rbt is None or rbt.n_out != feat.shape[0] or rbt.kvol != rb.kvol:
+                raise ImfError("DenseConvFunction: the input gradient needs the opposite table of the forward's")
+            wt = weight.detach().float().permute(2, 3, 0, 1).reshape(rb.kvol, co, ci)
+            if ctx.flip:
+                wt = wt.flip(0)
+            variant = training_variant(rb.kvol)
+            grad_feat = ops.spconv(g, ops.pack_weights(wt.contiguous(), variant=variant), ci, rbt, variant=variant,
+                                   split_k=1, staging=_dense_staging(rb.kvol, ci))
+        if ctx.needs_input_grad[1]:
+            dw = spconv_wgrad(feat, g, rb, rb.kvol)                          # [k, ci, co]
+            grad_weight = dw.view(kh, kw, ci, co).permute(3, 2, 0, 1).contiguous().to(weight.dtype)
+        return grad_feat, grad_weight, None, None, None
+
+
+class MaxPoolRowsFunction(torch.autograd.Function):
+    """(out, tap) = nn.MaxPool2d(3, 2, 1) on the NHWC rows x [B*Hin*Win, C] (csrc/image_train.hip): ties go to the first
+    maximum in (ky, kx) order as in torch; tap (uint8, not differentiable) is the winner per element.  The backward
+    gathers: no atomics."""
+
+    @staticmethod
+    def forward(ctx, x, B, Hin, Win):
+        out, tap = ops.image_maxpool_forward(x.detach().contiguous(), B, Hin, Win)
+        ctx.save_for_backward(tap)
+        ctx.shape = (B, Hin, Win)
+        ctx.mark_non_differentiable(tap)
+        return out, tap
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_tap):
+        (tap,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return ops.image_maxpool_backward(grad_out.contiguous().float(), tap, *ctx.shape), None, None, None
 
 
 class SparseBatchNormFunction(torch.autograd.Function):

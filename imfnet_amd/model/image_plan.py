@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import ImageDesc, check
+from .image_encoder import trunk_supported
 
 
 def _fold(bn):
@@ -27,9 +28,7 @@ class ImagePlan:
     def __init__(self, img_encoder, cross_block, variant):
         self.L = _lib.lib()
         bb = img_encoder.backbone
-        self.supported = (len(bb.layer1) == 3 and len(bb.layer2) == 4 and bb.conv1.weight.is_cuda and
-                          bb.conv1.weight.shape == (64, 3, 7, 7) and bb.layer2[0].downsample is not None and
-                          all(b.downsample is None for b in list(bb.layer1) + list(bb.layer2)[1:]))
+        self.supported = trunk_supported(bb)
         if not self.supported:
             return
         self.variant = int(variant)

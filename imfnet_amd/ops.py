@@ -984,6 +984,116 @@ def fusion_train_backward(dz, x, item_starts, tokens, weights, saved, want_dx=Tr
     return dx, dtok, grads, meta
 
 
+# The image encoder of training (env IMF_TRAIN_IMAGE; python -m imfnet_amd.train --image_kernels):
+#   "torch" (default) = the torch modules of model/image_encoder.py (MIOpen / aten convolutions, BatchNorm2d, max pool),
+#                       differentiated by torch's autograd;
+#   "hip"             = the trunk on NHWC rows: autograd.DenseConvFunction (imf_spconv_fwd / imf_spconv_wgrad over the
+#                       static pixel tables of csrc/image_train.hip), autograd.SparseBatchNormFunction with the block's
+#                       ReLU and residual add folded in, autograd.MaxPoolRowsFunction: fixed summation orders, no
+#                       floating-point atomics, bit-reproducible.  Used only in training mode under autograd on an fp32
+#                       GPU image that needs no gradient; every other call runs the torch modules whatever the switch.
+TRAIN_IMAGE_CHOICES = ("torch", "hip")
+TRAIN_IMAGE = os.environ.get("IMF_TRAIN_IMAGE", "torch")
+if TRAIN_IMAGE not in TRAIN_IMAGE_CHOICES:
+    raise ImfError(f"IMF_TRAIN_IMAGE={TRAIN_IMAGE!r}: one of {', '.join(TRAIN_IMAGE_CHOICES)}")
+
+
+def set_train_image(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_IMAGE
+    if name not in TRAIN_IMAGE_CHOICES:
+        raise ImfError(f"image kernels {name!r}: one of {', '.join(TRAIN_IMAGE_CHOICES)}")
+    prev, TRAIN_IMAGE = TRAIN_IMAGE, name
+    return prev
+
+
+def image_trunk_shapes(H, W):
+    """((H2, W2), (H4, W4), (H8, W8)): the stem's, the pool's and layer2's maps of an H x W image."""
+    down = lambda v, k, p: (v + 2 * p - k) // 2 + 1                         # noqa: E731
+    h2, w2 = down(H, 7, 3), down(W, 7, 3)
+    h4, w4 = down(h2, 3, 1), down(w2, 3, 1)
+    return (h2, w2), (h4, w4), (down(h4, 3, 1), down(w4, 3, 1))
+
+
+class ImageTrainTables:
+    """The six static pixel tables of imf_image_train_tables_build for (B, H, W) images on `device`, each an
+    `ops.Rulebook` over views of one storage tensor: t4, t48, t48T, td, tdT, t8 (include/imfnet_hip.h says what each is),
+    plus `stem`, the identity 'rulebook' of the stem's pointwise convolution over the im2col rows."""
+
+    def __init__(self, B, H, W, device):
+        L = _lib.lib()
+        nbytes = L.imf_image_train_tables_bytes(B, H, W)
+        if nbytes == 0:
+            raise ImfError(f"image tables: B={B} H={H} W={W} (B >= 1, H and W >= 8)")
+        self.B, self.H, self.W = B, H, W
+        self.shapes = image_trunk_shapes(H, W)
+        self.storage = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        c = _lib.ImageTrainTables()
+        with torch.cuda.device(self.storage.device):
+            check(L.imf_image_train_tables_build(B, H, W, self.storage.data_ptr(), nbytes, C.byref(c), _stream()),
+                  "imf_image_train_tables_build")
+        base = self.storage.data_ptr()
+
+        def view(addr, words):
+            off = addr - base
+            return self.storage[off:off + 4 * words].view(torch.int32)
+
+        for name in _lib.IMAGE_TRAIN_TABLES:
+            t = getattr(c, name)
+            setattr(self, name, Rulebook(view(t.tile_rows, t.n_slots), view(t.nbr, t.kvol * t.n_slots),
+                                         view(t.tile_mask, t.n_slots // TILE_ROWS * MASK_WORDS), t.n_slots, t.n_out, t.kvol))
+        self.stem = rulebook_identity(B * self.shapes[0][0] * self.shapes[0][1], device)
+
+
+def image_im2col7(image):
+    """imf_image_im2col7: [B,3,H,W] fp32 -> the stem's patch matrix [B*H2*W2, 160]."""
+    _req(image, torch.float32, "image", 4)
+    B, ch, H, W = image.shape
+    if ch != 3:
+        raise ImfError(f"image must be [B,3,H,W], got {tuple(image.shape)}")
+    (h2, w2), _, _ = image_trunk_shapes(H, W)
+    out = torch.empty((B * h2 * w2, 160), dtype=torch.float32, device=image.device)
+    with torch.cuda.device(image.device):
+        check(_lib.lib().imf_image_im2col7(image.data_ptr(), B, H, W, out.data_ptr(), _stream()), "imf_image_im2col7")
+    return out
+
+
+def _pool_rows(t, dtype, name, rows, c):
+    _req(t, dtype, name, 2)
+    if tuple(t.shape) != (rows, c):
+        raise ImfError(f"{name} must be [{rows}, {c}], got {tuple(t.shape)}")
+    return t
+
+
+def image_maxpool_forward(x, B, Hin, Win):
+    """imf_image_maxpool_forward: NHWC rows x [B*Hin*Win, C] -> (out [B*Hout*Wout, C], tap uint8 of the same shape)."""
+    c = x.shape[1] if torch.is_tensor(x) and x.dim() == 2 else 0
+    _pool_rows(x, torch.float32, "x", B * Hin * Win, c)
+    rows = B * ((Hin - 1) // 2 + 1) * ((Win - 1) // 2 + 1)
+    out = torch.empty((rows, c), dtype=torch.float32, device=x.device)
+    tap = torch.empty((rows, c), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().imf_image_maxpool_forward(x.data_ptr(), B, Hin, Win, c, out.data_ptr(), tap.data_ptr(), _stream()),
+              "imf_image_maxpool_forward")
+    return out, tap
+
+
+def image_maxpool_backward(dout, tap, B, Hin, Win, din=None):
+    """imf_image_maxpool_backward: din [B*Hin*Win, C], written whole (`din` may be given)."""
+    c = dout.shape[1] if torch.is_tensor(dout) and dout.dim() == 2 else 0
+    rows = B * ((Hin - 1) // 2 + 1) * ((Win - 1) // 2 + 1)
+    _pool_rows(dout, torch.float32, "dout", rows, c)
+    _pool_rows(tap, torch.uint8, "tap", rows, c)
+    if din is None:
+        din = torch.empty((B * Hin * Win, c), dtype=torch.float32, device=dout.device)
+    else:
+        _pool_rows(din, torch.float32, "din", B * Hin * Win, c)
+    with torch.cuda.device(dout.device):
+        check(_lib.lib().imf_image_maxpool_backward(dout.data_ptr(), tap.data_ptr(), B, Hin, Win, c, din.data_ptr(),
+                                                    _stream()), "imf_image_maxpool_backward")
+    return din
+
+
 def dam_heat(out_prenorm, hidden, targets, accumulate=True, n_dev=None, heat=None):
     """imf_dam_heat (csrc/dam.hip): Descriptor Activation Mapping of T target rows at once.  out_prenorm [N, 32] = the
     output of `final` before normalisation, hidden [N, c_hid] = its input, targets int32 [T] on the device.  Returns

@@ -116,6 +116,9 @@ def make_parser():
     a("--fusion_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="the bottleneck point <-> image attention block and its gradients: torch ops per batch item, or the "
            "deterministic HIP kernels (all items in one call, fixed summation order, no host wait)")
+    a("--image_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="the image encoder (16 convolutions, 16 BatchNorm2d, the max pool) and its gradients: torch modules, or the "
+           "deterministic HIP kernels over static pixel tables (fixed summation order, no floating-point atomics)")
     return p
 
 
@@ -172,6 +175,7 @@ class HardestContrastiveTrainer:
         ops.set_train_norm(getattr(config, "norm_kernels", "torch"))
         ops.set_train_loss(getattr(config, "loss_kernels", "torch"))
         ops.set_train_fusion(getattr(config, "fusion_kernels", "torch"))
+        ops.set_train_image(getattr(config, "image_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)

@@ -514,6 +514,57 @@ int imf_image_branch(const imf_image_desc *net /* [host] */, const float *image,
                      float *v_packed, int tokens_padded, int32_t *flags /* device, optional: IMF_FLAG_RANGE */,
                      void *stream);
 
+/* ---- Training of the image trunk (csrc/image_train.hip) -------------------------------------------------------------------
+ * Replaces: ImageEncoder / ResNet.forward in training mode and its autograd (model/resnet.py:195-216 under
+ *           loss.backward(), lib/trainer.py:495-569): 16 MIOpen convolutions, 16 training-mode BatchNorm2d, the max pool
+ *           and their gradients.  The convolutions are imf_spconv_fwd (forward, and input gradient over the opposite
+ *           table) and imf_spconv_wgrad over the static pixel tables below, BatchNorm2d over NCHW is imf_bn_train_* over
+ *           the [B*H*W, C] rows (imfnet_amd/autograd.py, model/image_encoder.py); this section adds the tables, the stem's
+ *           im2col and the max pool.  Every call takes a stream and synchronises nothing; bad arguments (B < 1, H or W < 8,
+ *           a null pointer, a short or misaligned buffer, C % 4 != 0) return IMF_EINVAL before any launch.
+ *
+ * Tables.  With H2 x W2 the stem's output ((H - 1) / 2 + 1), H4 x W4 the pool's, H8 x W8 layer2's, rows = NHWC pixels
+ * (b * H + y) * W + x, taps k = ky * 3 + kx, nbr[k * n_slots + slot] = the pixel the row gathers through tap k or -1, slots
+ * beyond n_out padding (tile_rows -1, nbr -1), tile_mask bit k of a 64-slot tile set when any of its rows has a neighbour
+ * through tap k -- the layout imf_conv_args reads:
+ *   t4    rows H4 x W4  from H4 x W4  9 taps  3x3 stride 1 pad 1 (layer1); its own opposite with taps k <-> 8 - k
+ *   t48   rows H8 x W8  from H4 x W4  9 taps  3x3 stride 2 pad 1 (layer2.0.conv1)
+ *   t48T  rows H4 x W4  from H8 x W8  9 taps  opposite of t48: nbrT[k][i] = o  <=>  nbr[k][o] = i
+ *   td    rows H8 x W8  from H4 x W4  1 tap   1x1 stride 2 (layer2.0.downsample)
+ *   tdT   rows H4 x W4  from H8 x W8  1 tap   opposite of td: a pixel with an odd coordinate has no neighbour.  Its mask
+ *         has tap 0 set in EVERY tile that holds a row, so that imf_spconv_fwd (which skips a tile with an empty mask)
+ *         writes +0.0 to those pixels
+ *   t8    rows H8 x W8  from H8 x W8  9 taps  3x3 stride 1 pad 1 (layer2); its own opposite likewise
+ * The six tables depend on (B, H, W) only and live in the caller's storage (imf_image_train_tables_bytes, 256-byte
+ * aligned); `out` [host] receives their device addresses and counts.  Integer work: the same tables every time. */
+typedef struct imf_image_table {
+  int32_t *tile_rows, *nbr;
+  uint32_t *tile_mask;
+  int64_t n_slots, n_out;
+  int32_t kvol;
+} imf_image_table;
+typedef struct imf_image_train_tables {
+  imf_image_table t4, t48, t48T, td, tdT, t8;
+} imf_image_train_tables;
+size_t imf_image_train_tables_bytes(int B, int H, int W);   /* 0 for a shape the build refuses */
+int imf_image_train_tables_build(int B, int H, int W, void *storage, size_t storage_bytes,
+                                 imf_image_train_tables *out /* [host] */, void *stream);
+/* The stem's patch matrix: image [B,3,H,W] fp32 -> out [B*H2*W2, 160], column (ky*7+kx)*3 + ch = the pixel the 7x7 / 2 /
+ * pad 3 convolution reads there (0 outside the image), columns 147..159 zero -- the matrix imf_image_branch builds, without
+ * its range flag.  A copy: exact. */
+int imf_image_im2col7(const float *image_nchw, int B, int H, int W, float *out, void *stream);
+/* nn.MaxPool2d(3, 2, 1) (model/resnet.py:144,202) on NHWC rows in [B*Hin*Win, C] -> out [B*Hout*Wout, C], Hout = (Hin - 1) /
+ * 2 + 1; C % 4 == 0, 16-byte aligned rows.  The taps inside the map are scanned in (ky, kx) row-major order and a later one
+ * replaces the current one only when it is strictly greater (torch's rule: among equal maxima the FIRST receives the
+ * gradient) or NaN (a NaN in a window gives NaN; which tap then receives the gradient is unspecified).  tap [B*Hout*Wout, C]
+ * uint8 = ky*3+kx of the winner.
+ * backward: one thread per input pixel and 4 channels gathers dout from the at most four windows that contain the pixel,
+ * in ascending (oy, ox) order, where tap points at it; fp64 sum, one rounding; every element of din [B*Hin*Win, C] is
+ * written, zeros included.  No atomics: two calls give the same bits. */
+int imf_image_maxpool_forward(const float *in, int B, int Hin, int Win, int C, float *out, uint8_t *tap, void *stream);
+int imf_image_maxpool_backward(const float *dout, const uint8_t *tap, int B, int Hin, int Win, int C, float *din,
+                               void *stream);
+
 /* imf_fusion_attention_batched + IMF_FLAG_RANGE on the output rows (they feed conv4_tr); flags may be NULL. */
 int imf_fusion_attention_batched_flags(const float *x, int n_items, const int64_t *item_row0, const int64_t *item_rows,
                                        const float *const *kt_packed, const float *const *v_packed, int n_tokens,

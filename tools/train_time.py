@@ -16,7 +16,7 @@ rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).quer
 (one thread) for the same sets.
 
 Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
-       [--fusion_kernels torch|hip] [--out FILE.json]
+       [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -88,6 +88,7 @@ def main():
     ap.add_argument("--norm_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--loss_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--fusion_kernels", default="torch", choices=("torch", "hip"))
+    ap.add_argument("--image_kernels", default="torch", choices=("torch", "hip"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -100,7 +101,7 @@ def main():
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
                             "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out"),
                             "--norm_kernels", a.norm_kernels, "--loss_kernels", a.loss_kernels,
-                            "--fusion_kernels", a.fusion_kernels])
+                            "--fusion_kernels", a.fusion_kernels, "--image_kernels", a.image_kernels])
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -121,6 +122,7 @@ def main():
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
     res.update(norm_kernels=a.norm_kernels, loss_kernels=a.loss_kernels, fusion_kernels=a.fusion_kernels,
+               image_kernels=a.image_kernels,
                batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
     ang = np.deg2rad(4.0)
