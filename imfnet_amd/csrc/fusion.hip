@@ -56,7 +56,7 @@ __device__ __forceinline__ bool fusion_item_rows(const FusionParams &p, int item
   n = n < p.n ? n : p.n;
   const int s0 = p.starts_dev[item];
   const int s1 = item + 1 < p.n_items ? p.starts_dev[item + 1] : (int)n;
-  if (s0 < 0 || s1 < s0) {          // an item without rows: flagged, as the exact-size path raises
+  if (s0 < 0 || s1 <= s0) {         // an item without rows (absent: start -1, or empty: s1 == s0): flagged, as the exact-size path refuses it
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(p.err, 8);
     return false;
   }
@@ -391,6 +391,14 @@ int imf_fusion_attention_dyn(const float *x, int64_t n_cap, const int32_t *n_dev
                                        tokens_padded, w, scale, out, workspace, workspace_bytes, stream, 0);
 }
 
+int imf_fusion_attention_dyn_v(const float *x, int64_t n_cap, const int32_t *n_dev, const int32_t *item_starts_dev,
+                               int n_items, int32_t *err, const float *const *kt_packed, const float *const *v_packed,
+                               int n_tokens, int tokens_padded, const imf_fusion_weights *w, float scale, float *out,
+                               void *workspace, size_t workspace_bytes, int variant, void *stream) {
+  return imf::fusion_attention_dyn_fmt(x, n_cap, n_dev, item_starts_dev, n_items, err, kt_packed, v_packed, n_tokens,
+                                       tokens_padded, w, scale, out, workspace, workspace_bytes, stream, 0, variant);
+}
+
 }  // extern "C"
 
 namespace imf {
@@ -401,6 +409,8 @@ int fusion_attention_dyn_fmt(const float *x, int64_t n_cap, const int32_t *n_dev
   IMF_REQUIRE(x && n_dev && item_starts_dev && err && kt_packed && v_packed && w && out && workspace,
               "imf_fusion_attention_dyn: null pointer");
   IMF_REQUIRE(n_items >= 1 && n_items <= IMF_MAX_BATCH && n_cap > 0, "imf_fusion_attention_dyn: n_items=%d", n_items);
+  IMF_REQUIRE(w->ln1_g && w->ln1_b && w->wq_p && w->wo_p && w->bo && w->ln2_g && w->ln2_b && w->w1_p && w->b1 &&
+                  w->w2_p && w->b2, "imf_fusion_attention_dyn: null weight pointer");
   IMF_REQUIRE(tokens_padded % 64 == 0 && tokens_padded <= kMaxTokP && n_tokens > 0 && n_tokens <= tokens_padded,
               "imf_fusion_attention_dyn: tokens=%d padded=%d", n_tokens, tokens_padded);
   IMF_REQUIRE(workspace_bytes >= imf_fusion_workspace_bytes_cap(n_cap) && aligned16(workspace),

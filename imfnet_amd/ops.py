@@ -691,6 +691,32 @@ def fusion_attention_batched(x, items, kt_packed, v_packed, n_tokens, tokens_pad
     return out
 
 
+def fusion_attention_dyn(x, n_dev, item_starts_dev, n_items, kt_packed, v_packed, n_tokens, tokens_padded, fw, out, flags,
+                         variant=None):
+    """Capacity mode of `fusion_attention_batched` (imf_fusion_attention_dyn_v): x and out [n_cap, 256], the row count in
+    n_dev (device int32[1]) and the items' first rows in item_starts_dev (device int32[n_items]; the last item ends at the
+    count).  Rows of `out` from the count on are not written.  flags: device int32[1], required -- bit 3 (value 8) for an
+    item without rows, IMF_FLAG_RANGE as in the exact call."""
+    _req(x, torch.float32, "x", 2)
+    _req(out, torch.float32, "out", 2)
+    if out.shape != x.shape or n_dev.dtype != torch.int32 or item_starts_dev.dtype != torch.int32 or \
+            item_starts_dev.numel() < n_items or flags is None or flags.dtype != torch.int32:
+        raise ImfError("fusion_attention_dyn: out as x; n_dev, item_starts_dev [n_items] and flags are device int32")
+    if variant is None:
+        variant = CONV_VARIANT if CONV_VARIANT in (6, 3) else 0
+    B = int(n_items)
+    L = _lib.lib()
+    kp = (C.c_void_p * B)(*[t.data_ptr() for t in kt_packed])
+    vp = (C.c_void_p * B)(*[t.data_ptr() for t in v_packed])
+    nbytes = L.imf_fusion_workspace_bytes_cap(x.shape[0])
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+    check(L.imf_fusion_attention_dyn_v(x.data_ptr(), x.shape[0], n_dev.data_ptr(), item_starts_dev.data_ptr(), B,
+                                       flags.data_ptr(), kp, vp, int(n_tokens), int(tokens_padded), C.byref(fw.c),
+                                       C.c_float(fw.scale), out.data_ptr(), ws.data_ptr(), nbytes, int(variant), _stream()),
+          "imf_fusion_attention_dyn")
+    return out
+
+
 def fusion_attention(x, kt_packed, v_packed, n_tokens, tokens_padded, fw, out=None, flags=None, variant=None):
     """x [n,256] -> [n,256]: the fusion block for one image (attention kernel + the two feed-forward GEMMs on the conv
     kernels); flags / variant as in `fusion_attention_batched`."""

@@ -457,7 +457,10 @@ int imf_fusion_attention(const float *x, int64_t n, const float *kt_packed, cons
                          float scale, float *out, void *workspace, size_t workspace_bytes, void *stream);
 /* Batched form (one image per batch item, model/resunet.py:241-250): rows [item_row0[b], +item_rows[b]) of x
  * attend to the tokens of image b (kt_packed[b], v_packed[b]); arrays are [host], n_items <= IMF_MAX_BATCH.
- * Workspace as imf_fusion_workspace_bytes(total rows). */
+ * Workspace as imf_fusion_workspace_bytes(total rows).
+ * Padding: the columns of K^T and the rows of V in [n_tokens, tokens_padded) may hold any FINITE values -- their scores
+ * never enter the softmax and their probabilities are exactly 0, so the output's bits do not depend on them.  Non-finite
+ * padding is outside the contract (0 x inf in the P V product). */
 int imf_fusion_attention_batched(const float *x, int n_items, const int64_t *item_row0, const int64_t *item_rows,
                                  const float *const *kt_packed, const float *const *v_packed, int n_tokens,
                                  int tokens_padded, const imf_fusion_weights *w /* [host] */, float scale, float *out,
@@ -579,6 +582,12 @@ int imf_fusion_attention_dyn(const float *x, int64_t n_cap, const int32_t *n_dev
                              int n_items, int32_t *err, const float *const *kt_packed, const float *const *v_packed,
                              int n_tokens, int tokens_padded, const imf_fusion_weights *w /* [host] */, float scale,
                              float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the arithmetic of the feed-forward chosen, as imf_fusion_attention_batched_v chooses it (6, 3 or 0;
+ * imf_fusion_attention_dyn is variant 6). */
+int imf_fusion_attention_dyn_v(const float *x, int64_t n_cap, const int32_t *n_dev, const int32_t *item_starts_dev,
+                               int n_items, int32_t *err, const float *const *kt_packed, const float *const *v_packed,
+                               int n_tokens, int tokens_padded, const imf_fusion_weights *w /* [host] */, float scale,
+                               float *out, void *workspace, size_t workspace_bytes, int variant, void *stream);
 
 /* ---- Native executor for the ResUNet layer schedule -----------------------------------------------
  * One call per fragment replaces the ~100 per-layer calls of model/resunet.py:163-235 (rulebook builds

@@ -36,16 +36,14 @@ def _ln_bwd(dn, xh, rstd, g):
     return dx, (dn * xh).sum(lead), dn.sum(lead)
 
 
-def forward(x, starts, tokens, params):
-    """z [n, 256] and the cache for `backward`."""
-    x, tokens = _f64(x), _f64(tokens)
+def forward_from_kv(x, starts, k, v, params):
+    """(z [n, 256], the intermediates) of everything after K / V: k, v [B, T, 128] as given (the inference entry points of
+    csrc/fusion.hip take them packed); the context LayerNorm and to_kv parameters of `params` are not read."""
+    x, k, v = _f64(x), _f64(k), _f64(v)
     P = [_f64(p) for p in params]
     starts = [int(s) for s in starts]
-    B, T, _ = tokens.shape
-    assert len(starts) == B + 1 and starts[0] == 0 and starts[-1] == x.shape[0]
-    c, ch, crstd = _ln(tokens, P[LNC_G], P[LNC_B])
-    kv = c @ P[WKV].T
-    k, v = kv[..., :INNER], kv[..., INNER:]                      # K first, V second
+    B, T, _ = k.shape
+    assert v.shape == k.shape and len(starts) == B + 1 and starts[0] == 0 and starts[-1] == x.shape[0]
     n1, xh1, rstd1 = _ln(x, P[LN1_G], P[LN1_B])
     q = n1 @ P[WQ].T
     p = np.zeros((x.shape[0], T))
@@ -63,8 +61,20 @@ def forward(x, starts, tokens, params):
     cdf = 0.5 * (1.0 + _erf(g / math.sqrt(2.0)))
     u = a * (g * cdf)
     z = u @ P[W2].T + P[B2] + y
-    cache = dict(P=P, starts=starts, c=c, ch=ch, crstd=crstd, k=k, v=v, n1=n1, xh1=xh1, rstd1=rstd1, q=q, p=p, o=o,
-                 xh2=xh2, rstd2=rstd2, n2=n2, a=a, g=g, cdf=cdf, u=u, tokens_shape=tokens.shape)
+    return z, dict(P=P, starts=starts, k=k, v=v, n1=n1, xh1=xh1, rstd1=rstd1, q=q, p=p, o=o, xh2=xh2, rstd2=rstd2, n2=n2,
+                   a=a, g=g, cdf=cdf, u=u)
+
+
+def forward(x, starts, tokens, params):
+    """z [n, 256] and the cache for `backward`."""
+    tokens = _f64(tokens)
+    P = [_f64(p) for p in params]
+    assert len(starts) == tokens.shape[0] + 1
+    c, ch, crstd = _ln(tokens, P[LNC_G], P[LNC_B])
+    kv = c @ P[WKV].T
+    k, v = kv[..., :INNER], kv[..., INNER:]                      # K first, V second
+    z, cache = forward_from_kv(x, starts, k, v, P)
+    cache.update(c=c, ch=ch, crstd=crstd, tokens_shape=tokens.shape)
     return z, cache
 
 
