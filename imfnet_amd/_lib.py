@@ -175,6 +175,20 @@ class Job(C.Structure):
                 ("defer_download", C.c_int32)]
 
 
+SGD_PLAIN, SGD_ME, SGD_TORCH = 0, 1, 2      # imf_sgd_record.layout
+SGD_CHUNK = 2048
+
+
+class SgdRecord(C.Structure):
+    """struct imf_sgd_record (include/imfnet_hip.h); imf_sgd_record_layout reports the library's own offsets and sizes
+    (tests/test_optim_host.py holds this mirror against them)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum", C.c_void_p),
+                ("image_fwd", C.c_void_p), ("image_bwd", C.c_void_p),
+                ("numel", C.c_int64),
+                ("first_step", C.c_int32), ("layout", C.c_int32),
+                ("kvol", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32), ("flip", C.c_int32)]
+
+
 PIPELINE_SDMA_COPIES = 1
 
 _P, _I, _L, _D, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t
@@ -200,6 +214,9 @@ SIGNATURES = {
     "imf_fusion_train_forward": (_I, [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _P, _Z, _P, _P]),
     "imf_fusion_train_backward": (_I, [_P, _P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _Z, _P, _P,
                                        C.POINTER(C.c_void_p), _P, _P, _Z, _P]),
+    "imf_sgd_chunk": (_I, []),
+    "imf_sgd_record_layout": (_I, [_I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "imf_sgd_step": (_I, [_P, _I, _P, _I, C.c_float, C.c_float, C.c_float, _P]),
     "imf_dam_heat": (_I, [_P, _L, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "imf_ply_vertex_count": (_L, [C.c_char_p]),
     "imf_ply_read_points": (_L, [C.c_char_p, _P, _L]),

@@ -65,6 +65,12 @@ def training_variant(kvol):
     return 3 if variant == 6 else variant
 
 
+def conv_flips_taps(module):
+    """Whether the input gradient of a sparse convolution runs on the kernel with its taps reversed: stride 1, not
+    transposed (the map is its own opposite).  The optimizer's backward images (train/optim.py) follow the same rule."""
+    return not module._transposed and module.stride == 1
+
+
 def spconv_wgrad(feat, grad_out, rb, kvol):
     """dW [kvol, cin, cout] of out = spconv(feat, W, rb)."""
     L = _lib.lib()
@@ -89,7 +95,7 @@ class SparseConvFunction(torch.autograd.Function):
             out = ops.spconv_small_cin(feat_c, k3.detach(), rb)
         else:
             variant = training_variant(module.kernel_volume)
-            out = ops.spconv(feat_c, ops.pack_weights(k3.detach(), variant=variant), module.out_channels, rb,
+            out = ops.spconv(feat_c, ops.weight_image(kernel, "forward", variant), module.out_channels, rb,
                              variant=variant)
         ctx.save_for_backward(feat_c, kernel)
         ctx.module, ctx.x, ctx.rb = module, x, rb
@@ -112,12 +118,9 @@ class SparseConvFunction(torch.autograd.Function):
                 grad_feat = g @ k3[0].t()
             else:
                 rbt = _opposite_rulebook(cm, ts, m.kernel_size, m.stride, m._transposed)
-                wt = k3.transpose(1, 2)
-                if not m._transposed and m.stride == 1:
-                    wt = wt.flip(0)
                 variant = training_variant(K)
-                grad_feat = ops.spconv(g, ops.pack_weights(wt.contiguous(), variant=variant), m.in_channels, rbt,
-                                       variant=variant)
+                wt = ops.weight_image(kernel, "backward", variant, flip=conv_flips_taps(m))
+                grad_feat = ops.spconv(g, wt, m.in_channels, rbt, variant=variant)
         if ctx.needs_input_grad[1]:
             dw = spconv_wgrad(feat, g, rb, K)
             grad_kernel = dw if kernel.dim() == 3 else dw[0]
@@ -144,9 +147,8 @@ class DenseConvFunction(torch.autograd.Function):
         if kh * kw != rb.kvol or feat.shape[1] != ci:
             raise ImfError(f"DenseConvFunction: weight {tuple(weight.shape)} on a {rb.kvol}-tap table over {feat.shape[1]} channels")
         feat_c = feat.detach().contiguous()
-        k3 = weight.detach().float().permute(2, 3, 1, 0).reshape(rb.kvol, ci, co).contiguous()
         variant = training_variant(rb.kvol)
-        out = ops.spconv(feat_c, ops.pack_weights(k3, variant=variant), co, rb, variant=variant, split_k=1,
+        out = ops.spconv(feat_c, ops.weight_image(weight, "forward", variant), co, rb, variant=variant, split_k=1,
                          staging=_dense_staging(rb.kvol, co))
         ctx.save_for_backward(feat_c, weight)
         ctx.rb, ctx.rb_opposite, ctx.flip = rb, rb_opposite, bool(flip)
@@ -162,12 +164,9 @@ class DenseConvFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if rbt is None or rbt.n_out != feat.shape[0] or rbt.kvol != rb.kvol:
                 raise ImfError("DenseConvFunction: the input gradient needs the opposite table of the forward's")
-            wt = weight.detach().float().permute(2, 3, 0, 1).reshape(rb.kvol, co, ci)
-            if ctx.flip:
-                wt = wt.flip(0)
             variant = training_variant(rb.kvol)
-            grad_feat = ops.spconv(g, ops.pack_weights(wt.contiguous(), variant=variant), ci, rbt, variant=variant,
-                                   split_k=1, staging=_dense_staging(rb.kvol, ci))
+            grad_feat = ops.spconv(g, ops.weight_image(weight, "backward", variant, flip=ctx.flip), ci, rbt,
+                                   variant=variant, split_k=1, staging=_dense_staging(rb.kvol, ci))
         if ctx.needs_input_grad[1]:
             dw = spconv_wgrad(feat, g, rb, rb.kvol)                          # [k, ci, co]
             grad_weight = dw.view(kh, kw, ci, co).permute(3, 2, 0, 1).contiguous().to(weight.dtype)

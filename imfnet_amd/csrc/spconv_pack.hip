@@ -11,6 +11,7 @@
 // guarded by IMF_FLAG_RANGE; the weights are split once, here, at pack time.  The kernels that consume the image:
 // spconv_g.hip (LDS-DMA staging, level 0 and the image branch), spconv_w.hip (wave-split, coarse levels), head.hip.
 #include "spconv_shared.h"
+#include "weight_image.h"
 
 namespace imf {
 
@@ -85,30 +86,20 @@ k_pack_weights_h3(const float *__restrict__ w, int kvol, int cin, int cout, _Flo
 // term down to 2^-16 relative; the three dropped ones are <= 2^-26 |a| |w| together), fp32 accumulation in the MFMA.
 // Image: [y][k][cc][q = 3 cb + part][lane][t] -- the split-f16 image's lane / channel mapping with three parts per
 // column block: ci = 32 cc + 16 (t >> 2) + 4 (lane >> 4) + (t & 3), co = y CW + 16 cb + (lane & 15); 1.5 x the fp32 size.
+// The index arithmetic and the split live in weight_image.h (the optimizer step of optim.hip writes the same image).
 __global__ void __launch_bounds__(256)
 k_pack_weights_b3(const float *__restrict__ w, int kvol, int cin, int cout, __bf16 *__restrict__ packed) {
   const long long total = (long long)kvol * cin * cout;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
-  const int CB = co_blk_of(cout), CW = 16 * CB, ncc = cin / 32;
-  long long r = idx;
-  const int t = r & 7; r >>= 3;
-  const int lane = r & 63; r >>= 6;
-  const int cb = r % CB; r /= CB;
-  const int cc = r % ncc; r /= ncc;
-  const int k = r % kvol; r /= kvol;
-  const int y = (int)r;
-  const int ci = cc * 32 + 16 * (t >> 2) + 4 * (lane >> 4) + (t & 3);
-  const int co = y * CW + 16 * cb + (lane & 15);
-  const float v = w[((long long)k * cin + ci) * cout + co];
-  const __bf16 p0 = (__bf16)v;
-  const float r1 = v - (float)p0;
-  const __bf16 p1 = (__bf16)r1;
-  const __bf16 p2 = (__bf16)(r1 - (float)p1);
-  const long long q0 = ((((long long)y * kvol + k) * ncc + cc) * (3 * CB) + 3 * cb) * 64 + lane;
-  packed[q0 * 8 + t] = p0;
-  packed[(q0 + 64) * 8 + t] = p1;
-  packed[(q0 + 128) * 8 + t] = p2;
+  const int t = (int)(idx & 7);
+  const B3Entry n = b3_entry_of(idx >> 3, kvol, cin, cout);
+  __bf16 p0, p1, p2;
+  b3_split(w[((long long)n.k * cin + b3_ci(n, t)) * cout + b3_co(n, cout)], p0, p1, p2);
+  __bf16 *const dst = packed + b3_entry_index(n, kvol, cin, cout) * 8 + t;
+  dst[0] = p0;
+  dst[kB3PartStride] = p1;
+  dst[2 * kB3PartStride] = p2;
 }
 
 }  // namespace imf

@@ -112,6 +112,20 @@ class ImageEncoder(nn.Module):
             norms.append(blk.bn2)
         return norms
 
+    def executed_convs(self):
+        """(convolution, flip) of the 15 convolutions `_forward_kernels` hands to DenseConvFunction with their own weight
+        (not the stem: its matrix is a derived tensor), `flip` as it passes it: the stride-1 ones run their input gradient
+        on the flipped taps.  train.optim.FusedSGD keeps the weight images of exactly these."""
+        bb = self.backbone
+        out = []
+        for blk in list(bb.layer1) + list(bb.layer2):
+            strided = blk.downsample is not None
+            out.append((blk.conv1, not strided))
+            out.append((blk.conv2, True))
+            if strided:
+                out.append((blk.downsample[0], False))
+        return out
+
     def _kernels_apply(self, x):
         """Whether this call takes the kernel path: the switch, training mode under autograd, an fp32 GPU image that
         needs no gradient, the backbone model/image_plan.py's ImagePlan supports, two rows or more at every stage."""

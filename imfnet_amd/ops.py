@@ -2,6 +2,7 @@
 memory and streams; every computation below happens in libimfnet_hip.so on the GPU."""
 import ctypes as C
 import os
+import weakref
 
 import torch
 
@@ -1151,3 +1152,121 @@ def dam_heat(out_prenorm, hidden, targets, accumulate=True, n_dev=None, heat=Non
                                       targets.data_ptr(), T, int(bool(accumulate)), weights.data_ptr(), heat.data_ptr(),
                                       minmax.data_ptr(), flags.data_ptr(), _stream()), "imf_dam_heat")
     return heat, minmax, flags, weights
+
+
+# The optimizer step of training (env IMF_TRAIN_OPTIM; python -m imfnet_amd.train --optim_kernels):
+#   "torch" (default) = torch.optim.SGD, and every differentiable convolution packs its weight images on every call;
+#   "hip"             = train.optim.FusedSGD: one imf_sgd_step launch over every parameter (csrc/optim.hip), which also
+#                       writes the two bf16x3 operand images of every packable convolution weight; `weight_image` hands
+#                       them to autograd.SparseConvFunction / DenseConvFunction while the parameter's `_version` is the one
+#                       the step left.  Torch does not move `_version` for writes through `.data` (`p.data.add_(1)`), so
+#                       a parameter with images is watched for `.data` accesses as well (_WatchedParameter below).
+TRAIN_OPTIM_CHOICES = ("torch", "hip")
+TRAIN_OPTIM = os.environ.get("IMF_TRAIN_OPTIM", "torch")
+if TRAIN_OPTIM not in TRAIN_OPTIM_CHOICES:
+    raise ImfError(f"IMF_TRAIN_OPTIM={TRAIN_OPTIM!r}: one of {', '.join(TRAIN_OPTIM_CHOICES)}")
+
+
+def set_train_optim(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_OPTIM
+    if name not in TRAIN_OPTIM_CHOICES:
+        raise ImfError(f"optim kernels {name!r}: one of {', '.join(TRAIN_OPTIM_CHOICES)}")
+    prev, TRAIN_OPTIM = TRAIN_OPTIM, name
+    return prev
+
+
+class WeightImages:
+    """The image pair an optimizer keeps for one convolution weight: `fwd` / `bwd` (either may be None) hold the bf16x3
+    images of the parameter as it was when its `_version` was `version`; `flip`: the backward image's taps are reversed."""
+    __slots__ = ("ref", "shape", "fwd", "bwd", "flip", "version", "key")
+
+    def __init__(self, param, fwd, bwd, flip):
+        self.ref, self.shape, self.fwd, self.bwd, self.flip = weakref.ref(param), tuple(param.shape), fwd, bwd, bool(flip)
+        self.version, self.key = -1, None
+
+
+_WEIGHT_IMAGES = {}                               # parameter data_ptr -> WeightImages (train.optim.FusedSGD registers them)
+
+
+_TENSOR_DATA = torch._C.TensorBase.data           # the `.data` descriptor every tensor inherits
+
+
+class _WatchedParameter(torch.nn.Parameter):
+    """The class of a parameter while an optimizer keeps images of it.  A write through `.data` moves no version counter
+    (the tensor `.data` returns has one of its own), so `_version` alone would let `p.data.add_(1)` pass unseen.  Here
+    every access to `.data`, read or assignment, marks the images stale until the next step -- conservative: whoever takes
+    `.data` may write through it.  Nothing on the training path takes it (forward, backward, state_dict, load_state_dict,
+    zero_grad, the step).  Still unseen: a write through a `.data` tensor taken BEFORE the step that wrote the images.
+    isinstance(p, nn.Parameter) holds, pickling gives a plain Parameter (torch's own __reduce_ex__)."""
+
+    @property
+    def data(self):
+        _data_taken(self)
+        return _TENSOR_DATA.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        _data_taken(self)
+        _TENSOR_DATA.__set__(self, value)
+
+
+def _data_taken(param):
+    for ent in _WEIGHT_IMAGES.values():
+        if ent.ref() is param:
+            ent.version = -1
+
+
+def register_weight_images(param, images):
+    images.key = param.data_ptr()
+    _WEIGHT_IMAGES[images.key] = images
+    if type(param) is torch.nn.Parameter:         # other subclasses keep their class (and the `.data` blind spot)
+        param.__class__ = _WatchedParameter
+
+
+def unregister_weight_images(images):
+    for key in [k for k, v in _WEIGHT_IMAGES.items() if v is images]:
+        del _WEIGHT_IMAGES[key]
+    param = images.ref()
+    if type(param) is _WatchedParameter and not any(e.ref() is param for e in _WEIGHT_IMAGES.values()):
+        param.__class__ = torch.nn.Parameter
+
+
+def weight_image(param, which, variant, flip=None):
+    """The packed operand image of a convolution weight for the differentiable convolutions: `which` = "forward" (the
+    image of the kernel itself) or "backward" (of the transposed kernel, its taps reversed when `flip`: the operand of the
+    input gradient).  `param`: an ME kernel [kvol, cin, cout] / [cin, cout] or a torch weight [cout, cin, kh, kw].
+    With ops.TRAIN_OPTIM == "hip" and variant 3, the image the optimizer wrote at its last step is returned while it is
+    still the parameter's (same storage, same `_version`, `.data` not taken since); in every other case the weight is packed here, by the torch
+    re-layout ops and the pack launch the convolutions always issued."""
+    if which not in ("forward", "backward"):
+        raise ImfError(f"weight_image: which={which!r}: 'forward' or 'backward'")
+    ent = _WEIGHT_IMAGES.get(param.data_ptr()) if (TRAIN_OPTIM == "hip" and variant == 3 and _WEIGHT_IMAGES) else None
+    if ent is not None and (ent.ref() is None or ent.shape != tuple(param.shape)):
+        ent = None
+    if ent is not None and ent.version == param._version:
+        img = ent.fwd if which == "forward" else ent.bwd
+        if img is not None and (which == "forward" or flip is None or bool(flip) == ent.flip):
+            return img
+    if which == "backward" and flip is None:
+        if ent is None:
+            raise ImfError("weight_image: the backward image of a weight no optimizer owns needs `flip`")
+        flip = ent.flip
+    return pack_weights(image_source(param, which, flip), variant=variant)
+
+
+def image_source(param, which, flip=False):
+    """The contiguous [kvol, cin', cout'] tensor whose packed image `weight_image` returns: the kernel itself ("forward"),
+    or its transpose W'[k'][co][ci] = W[k][ci][co] with k' = kvol - 1 - k when `flip` ("backward")."""
+    w = param.detach()
+    if w.dim() == 4:
+        co, ci, kh, kw = w.shape
+        k3 = (w.float().permute(2, 3, 1, 0).reshape(kh * kw, ci, co) if which == "forward"
+              else w.float().permute(2, 3, 0, 1).reshape(kh * kw, co, ci))
+    else:
+        k3 = w if w.dim() == 3 else w.unsqueeze(0)
+        if which == "backward":
+            k3 = k3.transpose(1, 2)
+    if which == "backward" and flip:
+        k3 = k3.flip(0)
+    return k3.contiguous()

@@ -4,7 +4,8 @@ config_kitti.py, train_3DMatch.py / train_Kitti.py) on the GPU.
 One training iteration: decode of the batch's files on at most 16 host threads (prefetched one batch ahead), then in
 this process on its stream: per item the random scale / rotation, voxelisation and positive-pair search
 (data.IndoorPairDataset.prepare), collate, one batched forward per side through `forward_layers` (training mode),
-the hardest-contrastive loss, backward and SGD.  No worker process opens the GPU and nothing forks.
+the hardest-contrastive loss, backward and SGD (`--optim_kernels hip`: train.optim.FusedSGD, one launch per step that
+also leaves the packed convolution weights).  No worker process opens the GPU and nothing forks.
 
 Kept from upstream: the option names and defaults, SGD with `momentum` (0.8; upstream ignores `sgd_momentum`),
 ExponentialLR(exp_gamma) stepped once per epoch, `iter_size` accumulation, validation every `val_epoch_freq` epochs
@@ -119,6 +120,9 @@ def make_parser():
     a("--image_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="the image encoder (16 convolutions, 16 BatchNorm2d, the max pool) and its gradients: torch modules, or the "
            "deterministic HIP kernels over static pixel tables (fixed summation order, no floating-point atomics)")
+    a("--optim_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="the SGD step: torch.optim.SGD, or one HIP launch over every parameter that also leaves the packed operand "
+           "images of the convolution weights, so that an iteration packs no weight again")
     return p
 
 
@@ -176,6 +180,7 @@ class HardestContrastiveTrainer:
         ops.set_train_loss(getattr(config, "loss_kernels", "torch"))
         ops.set_train_fusion(getattr(config, "fusion_kernels", "torch"))
         ops.set_train_image(getattr(config, "image_kernels", "torch"))
+        ops.set_train_optim(getattr(config, "optim_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)
@@ -187,8 +192,13 @@ class HardestContrastiveTrainer:
             sd, _ = load_checkpoint(config.weights)
             self.model.load_state_dict(sd)
         self.model = self.model.to(self.device)
-        self.optimizer = torch.optim.SGD(self.model.parameters(), lr=config.lr, momentum=config.momentum,
-                                         weight_decay=config.weight_decay)
+        if ops.TRAIN_OPTIM == "hip":
+            from .optim import FusedSGD                       # one launch per step; a checkpoint of either loads into both
+            self.optimizer = FusedSGD(self.model.parameters(), lr=config.lr, momentum=config.momentum,
+                                      weight_decay=config.weight_decay, model=self.model)
+        else:
+            self.optimizer = torch.optim.SGD(self.model.parameters(), lr=config.lr, momentum=config.momentum,
+                                             weight_decay=config.weight_decay)
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, config.exp_gamma)
         self.train_set, self.val_set = train_set, val_set
         self.start_epoch = 1

@@ -1164,6 +1164,48 @@ int imf_dam_heat(const float *out_prenorm, int64_t n, const int32_t *n_dev, cons
                  const int32_t *targets, int T, int accumulate, float *weights /* [T, 32] */, float *heat /* [T, n] */,
                  float *minmax /* [T, 2] */, int32_t *flags /* [T] */, void *stream);
 
+/* ---- The SGD step of training in one launch (csrc/optim.hip) -----------------------------------------------------------
+ * Replaces: torch.optim.SGD.step over the model's tensors (lib/trainer.py:62-66, 178) and, for the convolution weights, the
+ * re-packing of their operand images on every use.  Per element in fp32, each operation rounded once (no contraction):
+ *   d = g + wd p (wd == 0: d = g);  b' = mu b + d (first_step: b' = d; momentum NULL: no buffer, b' = d);  p' = p - lr b'
+ * = torch.optim.SGD with dampening 0, no Nesterov, not maximising.
+ * One record per tensor, in device memory.  param / grad / momentum: numel contiguous floats each.  layout:
+ *   IMF_SGD_PLAIN  any tensor, updated element-wise; the remaining fields are ignored;
+ *   IMF_SGD_ME     a convolution kernel [kvol, cin, cout] (2-D [cin, cout] when kvol == 1);
+ *   IMF_SGD_TORCH  a convolution weight [cout, cin, kh, kw], kvol = kh kw, tap k = kh_index kw + kw_index;
+ * the last two need cin % 32 == 0, cout % 32 == 0, 1 <= kvol <= 27, numel == kvol cin cout (the caller's to guarantee:
+ * the records live on the device) and also write, from the updated values, the bf16x3 images imf_pack_weights_bf16x3
+ * would build (imf_packed_weight_floats_bf16x3 floats each, 16-byte aligned; either may be NULL):
+ *   image_fwd  of W[k][ci][co];
+ *   image_bwd  of W'[k'][co][ci] = W[k][ci][co] with k' = kvol - 1 - k when flip != 0, else k' = k -- the operand of the
+ *              input gradient (the transposed kernel, its taps flipped for a stride-1 convolution). */
+#define IMF_SGD_PLAIN 0
+#define IMF_SGD_ME    1
+#define IMF_SGD_TORCH 2
+#define IMF_SGD_CHUNK 2048          /* elements of one tensor that one workgroup serves */
+#define IMF_SGD_RECORD_FIELDS 12
+typedef struct imf_sgd_record {
+  float *param;
+  const float *grad;
+  float *momentum;
+  float *image_fwd, *image_bwd;
+  int64_t numel;
+  int32_t first_step;
+  int32_t layout;
+  int32_t kvol, cin, cout;
+  int32_t flip;
+} imf_sgd_record;
+int imf_sgd_chunk(void);            /* IMF_SGD_CHUNK */
+/* Layout of imf_sgd_record as the library was compiled, for mirrors of the struct in other languages: field = 0 ..
+ * IMF_SGD_RECORD_FIELDS - 1 in declaration order gives that member's offset and size, field < 0 gives (0, sizeof). [host] */
+int imf_sgd_record_layout(int field, size_t *offset, size_t *size);
+/* One launch on `stream`, no host wait, no atomics.  block_map [n_blocks][2] int32 on the device: workgroup i serves
+ * elements [chunk IMF_SGD_CHUNK, (chunk + 1) IMF_SGD_CHUNK) of record block_map[i][0], chunk = block_map[i][1] (for a
+ * packable record: in the order of the forward image); every chunk of every record to be stepped exactly once, records
+ * left out are not touched.  n_blocks == 0 launches nothing. */
+int imf_sgd_step(const imf_sgd_record *records, int n_records, const int32_t *block_map, int n_blocks, float lr,
+                 float momentum, float weight_decay, void *stream);
+
 /* ---- Host-side codecs of the batch path: HOST pointers, no GPU involved ----------------------
  * Replace what the reference does around every fragment with Open3D / matplotlib / OpenCV / numpy
  * (scripts/generate_desc.py:83-97,118-123, util/uio.py:33-40).  All return 0 / a count on success, a negative

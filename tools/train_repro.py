@@ -2,8 +2,8 @@
 
 One hardest-contrastive training step (imfnet_amd/train) on the in-tree fixture pair, run twice in one process from the same
 seed -- a fresh data set and a fresh trainer each time, so the initialisation, the augmentation and the loss samples are the
-same -- with the four kernel switches (--norm_kernels, --loss_kernels, --fusion_kernels, --image_kernels) all at `hip`, and
-for contrast all at `torch`.  For every parameter: whether the two gradients agree bit for bit (a parameter without a
+same -- with the five kernel switches (--norm_kernels, --loss_kernels, --fusion_kernels, --image_kernels, --optim_kernels)
+all at `hip`, and for contrast all at `torch`.  For every parameter: whether the two gradients agree bit for bit (a parameter without a
 gradient in both runs counts as agreeing and is listed under `no_gradient`).
 
 Usage: python tools/train_repro.py [--batch 2] [--out FILE.json]
@@ -25,7 +25,7 @@ from train_time import write_tree                              # noqa: E402
 from imfnet_amd.train.data import IndoorPairDataset          # noqa: E402
 from imfnet_amd.train.trainer import HardestContrastiveTrainer, parse_config   # noqa: E402
 
-SWITCHES = ("norm_kernels", "loss_kernels", "fusion_kernels", "image_kernels")
+SWITCHES = ("norm_kernels", "loss_kernels", "fusion_kernels", "image_kernels", "optim_kernels")
 
 
 def one_step(root, batch, choice, tag):

@@ -7,7 +7,7 @@ and imf_radius_pairs against scipy's cKDTree.
   forward    the two batched training-mode forwards (forward_layers; --fusion_kernels hip: csrc/fusion_train.hip)
   loss       hardest-contrastive loss (sampling, two nn_search calls, masks; --loss_kernels hip: csrc/loss.hip)
   backward   loss.backward()
-  step       optimizer.step()
+  step       optimizer.step() (--optim_kernels hip: one launch of csrc/optim.hip, which also leaves the weight images)
   iteration  the sum
 The stages are separated by device synchronisations, so their sum is a little above a free-running iteration.
 
@@ -16,7 +16,7 @@ rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).quer
 (one thread) for the same sets.
 
 Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
-       [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--out FILE.json]
+       [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--optim_kernels torch|hip] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -36,6 +36,7 @@ from imfnet_amd.matching import radius_pairs                 # noqa: E402
 from imfnet_amd.train.data import IndoorPairDataset          # noqa: E402
 from imfnet_amd.train.trainer import HardestContrastiveTrainer, parse_config   # noqa: E402
 
+SWITCHES = ("norm_kernels", "loss_kernels", "fusion_kernels", "image_kernels", "optim_kernels")
 STAGES = ("decode", "geometry", "pairs", "forward", "loss", "backward", "step")
 
 
@@ -85,10 +86,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2)
-    ap.add_argument("--norm_kernels", default="torch", choices=("torch", "hip"))
-    ap.add_argument("--loss_kernels", default="torch", choices=("torch", "hip"))
-    ap.add_argument("--fusion_kernels", default="torch", choices=("torch", "hip"))
-    ap.add_argument("--image_kernels", default="torch", choices=("torch", "hip"))
+    for s in SWITCHES:
+        ap.add_argument("--" + s, default="torch", choices=("torch", "hip"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -99,9 +98,8 @@ def main():
     with tempfile.TemporaryDirectory() as root:
         write_tree(root, clouds, images)
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
-                            "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out"),
-                            "--norm_kernels", a.norm_kernels, "--loss_kernels", a.loss_kernels,
-                            "--fusion_kernels", a.fusion_kernels, "--image_kernels", a.image_kernels])
+                            "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out")] +
+                           [v for s in SWITCHES for v in ("--" + s, getattr(a, s))])
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -121,9 +119,9 @@ def main():
     for k in STAGES:
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
-    res.update(norm_kernels=a.norm_kernels, loss_kernels=a.loss_kernels, fusion_kernels=a.fusion_kernels,
-               image_kernels=a.image_kernels,
-               batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
+    res.update({s: getattr(a, s) for s in SWITCHES})
+    res["iteration_spread"] = float(np.ptp([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
+    res.update(batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
     ang = np.deg2rad(4.0)
     T[:3, :3] = [[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1]]
