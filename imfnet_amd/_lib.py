@@ -214,6 +214,11 @@ SIGNATURES = {
     "imf_fusion_train_forward": (_I, [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _P, _Z, _P, _P]),
     "imf_fusion_train_backward": (_I, [_P, _P, _L, _P, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_void_p), _P, _Z, _P, _P,
                                        C.POINTER(C.c_void_p), _P, _P, _Z, _P]),
+    "imf_head_train_chunk_rows": (_I, []),
+    "imf_head_train_workspace_bytes": (_Z, [_L]),
+    "imf_head_train_forward": (_I, [_P, _I, _P, _I, _L, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "imf_head_train_backward": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z,
+                                     _P, _P]),
     "imf_sgd_chunk": (_I, []),
     "imf_sgd_record_layout": (_I, [_I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "imf_sgd_step": (_I, [_P, _I, _P, _I, C.c_float, C.c_float, C.c_float, _P]),

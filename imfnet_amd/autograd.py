@@ -28,6 +28,10 @@ ResUNet2.transformer decides when it runs.
 (csrc/image_train.hip, ops.TRAIN_IMAGE == "hip"): the same three kernels as `SparseConvFunction` over static pixel tables,
 `SparseBatchNormFunction` between them; model.image_encoder.ImageEncoder decides when they run.
 
+`HeadFunction` is the descriptor head at the end of the decoder (csrc/head_train.hip, ops.TRAIN_HEAD == "hip"): the
+concatenation with the stride-1 skip, conv1_tr, ReLU, final and the L2 normalisation as one forward and one backward
+call; ResUNet2.forward_layers decides when it runs.
+
 Arithmetic: the training path never runs on a range-limited one.  Under the process-wide fast mode (ops.CONV_VARIANT 6,
 two f16 parts per operand) the forward and the input gradient here run on bf16x3 (variant 3: exact fp32 operands, fp32
 range) instead: gradients of the contrastive loss are routinely 1e-5 .. 1e-9, where f16 loses bits (below 6e-5) or
@@ -288,3 +292,29 @@ class AttentionFusionFunction(torch.autograd.Function):
         dx, dtok, grads, _meta = ops.fusion_train_backward(grad_out.contiguous().float(), xc, item_starts, tc, weights,
                                                            saved, need[0], need[2], need[3:])
         return (dx, None, dtok, *grads)
+
+
+class HeadFunction(torch.autograd.Function):
+    """y = the descriptor head of forward_layers on feature rows (csrc/head_train.hip, ops.TRAIN_HEAD == "hip"):
+    relu(cat(u, s) @ w1) @ w2 + bias, divided by its rows' L2 norms when `normalize`.  u [n, 64], s [n, 32], w1 [96, 64]
+    (conv1_tr.kernel), w2 [64, 32] and bias [1, 32] (final).  Saves u, s, h, r, y; the backward computes only the gradients
+    autograd asks for; nothing on either way waits for the device."""
+
+    @staticmethod
+    def forward(ctx, u, s, w1, w2, bias, normalize):
+        uc, sc = u.detach().contiguous(), s.detach().contiguous()
+        w1c, w2c, bc = w1.detach().contiguous(), w2.detach().contiguous(), bias.detach().contiguous()
+        h, r, y, _meta = ops.head_train_forward(uc, sc, w1c, w2c, bc, normalize)
+        ctx.normalize = bool(normalize)
+        ctx.save_for_backward(uc, sc, h, r, y, w1c, w2c)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        u, s, h, r, y, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad[:5]
+        if not any(need):
+            return (None,) * 6
+        du, ds, dw1, dw2, db, _meta = ops.head_train_backward(grad_out.contiguous().float(), y, r, h, u, s, w1, w2,
+                                                             ctx.normalize, want=need)
+        return du, ds, dw1, dw2, db, None

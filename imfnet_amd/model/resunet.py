@@ -427,12 +427,37 @@ class ResUNet2(ME.MinkowskiNetwork):
         out = MEF.relu(self.block3_tr(self.norm3_tr(self.conv3_tr(out))))
         out = ME.cat(out, out_s2)
         out = MEF.relu(self.block2_tr(self.norm2_tr(self.conv2_tr(out))))
+        if self._head_kernels_apply(out, out_s1):
+            # ops.TRAIN_HEAD == "hip": the lines below as one op, forward and backward in csrc/head_train.hip -- the
+            # concatenation is never built, every sum has a fixed order
+            from ..autograd import HeadFunction
+            return out._like(HeadFunction.apply(out.F, out_s1.F, self.conv1_tr.kernel, self.final.kernel, self.final.bias,
+                                                bool(self.normalize_feature)))
         out = ME.cat(out, out_s1)
         out = MEF.relu(self.conv1_tr(out))
         out = self.final(out)
         if self.normalize_feature:
             return out._like(out.F / torch.norm(out.F, p=2, dim=1, keepdim=True))
         return out
+
+    def _head_kernels_apply(self, out, out_s1):
+        """Whether the training kernels (csrc/head_train.hip) cover the head of this call: the switch, training mode with
+        autograd on, fp32 CUDA rows on one coordinate map, the one shape they implement, conv1_tr and final pointwise, the
+        first without a bias and the second with one.  Everything else runs the torch ops of `forward_layers`."""
+        if ops.TRAIN_HEAD != "hip" or not torch.is_grad_enabled() or not self.training:
+            return False
+        u, s = out.F, out_s1.F
+        if not (u.is_cuda and s.is_cuda and u.dtype == torch.float32 and s.dtype == torch.float32):
+            return False
+        if out.coordinate_map_key != out_s1.coordinate_map_key or u.dim() != 2 or s.dim() != 2 or u.shape[0] != s.shape[0]:
+            return False
+        c1, fin = self.conv1_tr, self.final
+        if c1.kernel_volume != 1 or fin.kernel_volume != 1 or c1.bias is not None or fin.bias is None:
+            return False
+        cu, cs, ch, co = ops.HEAD_TRAIN_DIMS
+        if (u.shape[1], s.shape[1]) != (cu, cs) or tuple(c1.kernel.shape) != (cu + cs, ch) or tuple(fin.kernel.shape) != (ch, co):
+            return False
+        return all(p.is_cuda and p.dtype == torch.float32 for p in (c1.kernel, fin.kernel, fin.bias))
 
     def _fusion_weights(self):
         self._refresh()

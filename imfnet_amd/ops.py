@@ -1011,6 +1011,104 @@ def fusion_train_backward(dz, x, item_starts, tokens, weights, saved, want_dx=Tr
     return dx, dtok, grads, meta
 
 
+# The descriptor head of training (env IMF_TRAIN_HEAD; python -m imfnet_amd.train --head_kernels):
+#   "torch" (default) = ME.cat, conv1_tr, ReLU, final, torch.norm and the division: the op sequence forward_layers always
+#                       had, differentiated by torch's autograd;
+#   "hip"             = csrc/head_train.hip through autograd.HeadFunction: one forward and one backward call, the
+#                       concatenation never built, fp32 MFMA products, the sums over a row's channels as fixed shuffle
+#                       trees and the sums over rows in a fixed chunk order, no floating-point atomics, no host wait,
+#                       bit-reproducible.  Used only in training mode under autograd on fp32 GPU rows of the one shape
+#                       ResUNetBN2C has; every other call runs the torch ops whatever the switch.
+TRAIN_HEAD_CHOICES = ("torch", "hip")
+TRAIN_HEAD = os.environ.get("IMF_TRAIN_HEAD", "torch")
+if TRAIN_HEAD not in TRAIN_HEAD_CHOICES:
+    raise ImfError(f"IMF_TRAIN_HEAD={TRAIN_HEAD!r}: one of {', '.join(TRAIN_HEAD_CHOICES)}")
+
+
+def set_train_head(name):
+    """Sets the process-wide switch; returns the previous value."""
+    global TRAIN_HEAD
+    if name not in TRAIN_HEAD_CHOICES:
+        raise ImfError(f"head kernels {name!r}: one of {', '.join(TRAIN_HEAD_CHOICES)}")
+    prev, TRAIN_HEAD = TRAIN_HEAD, name
+    return prev
+
+
+HEAD_TRAIN_DIMS = (64, 32, 64, 32)                # cu (decoder rows), cs (the stride-1 skip), ch (hidden), co (descriptor)
+HEAD_TRAIN_FLAG_NORM = 1                          # IMF_HT_FLAG_NORM of the meta word
+
+
+def head_train_chunk_rows():
+    return _lib.lib().imf_head_train_chunk_rows()
+
+
+def _head_train_args(u, s, w1, w2, bias=None):
+    """Dtypes, devices and shapes of the head's inputs; (n, cu, cs, ch, co).  The channel counts themselves are the
+    library's to refuse."""
+    _req(u, torch.float32, "u", 2)
+    _req(s, torch.float32, "s", 2)
+    _req(w1, torch.float32, "w1", 2)
+    _req(w2, torch.float32, "w2", 2)
+    n, cu, cs, (ch, co) = u.shape[0], u.shape[1], s.shape[1], w2.shape
+    if s.shape[0] != n or tuple(w1.shape) != (cu + cs, ch):
+        raise ImfError(f"s must be [{n}, cs] and w1 [{cu} + cs, {ch}], got {tuple(s.shape)} and {tuple(w1.shape)}")
+    if bias is not None and tuple(_req(bias, torch.float32, "bias", 2).shape) != (1, co):
+        raise ImfError(f"bias must be [1, {co}], got {tuple(bias.shape)}")
+    for name, t in (("s", s), ("w1", w1), ("w2", w2), ("bias", bias)):
+        if t is not None and t.device != u.device:
+            raise ImfError(f"{name} is on {t.device}, u on {u.device}")
+    return n, cu, cs, ch, co
+
+
+def head_train_forward(u, s, w1, w2, bias, normalize=True, out=None):
+    """imf_head_train_forward: (h [n, ch], r [n] or None without normalize, y [n, co], meta int32 [1]).  u [n, cu],
+    s [n, cs], w1 [cu + cs, ch], w2 [ch, co], bias [1, co].  meta[0] & HEAD_TRAIN_FLAG_NORM: a row's norm was 0 or not
+    finite; nothing here waits for it.  `out` = (h, r, y) may hand in the tensors to write."""
+    n, cu, cs, ch, co = _head_train_args(u, s, w1, w2, bias)
+    if out is None:
+        h = torch.empty((n, ch), dtype=torch.float32, device=u.device)
+        r = torch.empty((n,), dtype=torch.float32, device=u.device) if normalize else None
+        y = torch.empty((n, co), dtype=torch.float32, device=u.device)
+    else:
+        h, r, y = out
+        for name, t, shape in (("h", h, (n, ch)), ("r", r, (n,)), ("y", y, (n, co))):
+            if t is not None and (tuple(_req(t, torch.float32, name).shape) != shape or t.device != u.device):
+                raise ImfError(f"{name} must be {shape} on {u.device}")
+    meta = torch.zeros(1, dtype=torch.int32, device=u.device)
+    check(_lib.lib().imf_head_train_forward(_ptr(u), cu, _ptr(s), cs, n, w1.data_ptr(), ch, w2.data_ptr(), co,
+                                            bias.data_ptr(), int(bool(normalize)), _ptr(h), _ptr(r), _ptr(y),
+                                            meta.data_ptr(), _stream()), "imf_head_train_forward")
+    return h, r, y, meta
+
+
+def head_train_backward(dy, y, r, h, u, s, w1, w2, normalize=True, want=None, outputs=None):
+    """imf_head_train_backward: (du, ds, dw1, dw2, dbias, meta); None for what is not wanted (`want`: 5 booleans in that
+    order, default all).  `outputs` = (du, ds, dw1, dw2, dbias) may hand in the tensors to write (None: not wanted).
+    Without normalize, y and r may be None."""
+    n, cu, cs, ch, co = _head_train_args(u, s, w1, w2)
+    shapes = ((n, cu), (n, cs), (cu + cs, ch), (ch, co), (1, co))
+    names = ("du", "ds", "dw1", "dw2", "dbias")
+    for name, t, shape in (("dy", dy, (n, co)), ("h", h, (n, ch))) + ((("y", y, (n, co)), ("r", r, (n,))) if normalize else ()):
+        if tuple(_req(t, torch.float32, name).shape) != shape or t.device != u.device:
+            raise ImfError(f"{name} must be {shape} on {u.device}")
+    if outputs is None:
+        want = [True] * 5 if want is None else list(want)
+        outputs = [torch.empty(shape, dtype=torch.float32, device=u.device) if k else None for shape, k in zip(shapes, want)]
+    else:
+        for name, t, shape in zip(names, outputs, shapes):
+            if t is not None and (tuple(_req(t, torch.float32, name).shape) != shape or t.device != u.device):
+                raise ImfError(f"{name} must be {shape} on {u.device}")
+    L = _lib.lib()
+    nbytes = L.imf_head_train_workspace_bytes(n)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=u.device)
+    meta = torch.zeros(1, dtype=torch.int32, device=u.device)
+    check(L.imf_head_train_backward(_ptr(dy), _ptr(y) if normalize else None, _ptr(r) if normalize else None, _ptr(h),
+                                    _ptr(u), cu, _ptr(s), cs, n, w1.data_ptr(), ch, w2.data_ptr(), co,
+                                    int(bool(normalize)), *[_ptr(t) for t in outputs], ws.data_ptr(), nbytes,
+                                    meta.data_ptr(), _stream()), "imf_head_train_backward")
+    return (*outputs, meta)
+
+
 # The image encoder of training (env IMF_TRAIN_IMAGE; python -m imfnet_amd.train --image_kernels):
 #   "torch" (default) = the torch modules of model/image_encoder.py (MIOpen / aten convolutions, BatchNorm2d, max pool),
 #                       differentiated by torch's autograd;

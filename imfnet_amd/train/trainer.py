@@ -123,6 +123,10 @@ def make_parser():
     a("--optim_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="the SGD step: torch.optim.SGD, or one HIP launch over every parameter that also leaves the packed operand "
            "images of the convolution weights, so that an iteration packs no weight again")
+    a("--head_kernels", type=str, default="torch", choices=("torch", "hip"),
+      help="the descriptor head (concatenation with the stride-1 skip, conv1_tr, ReLU, final, L2 normalisation) and its "
+           "gradients: torch ops, or the deterministic HIP kernels (one forward and one backward call, fixed summation "
+           "order, no host wait)")
     return p
 
 
@@ -181,6 +185,7 @@ class HardestContrastiveTrainer:
         ops.set_train_fusion(getattr(config, "fusion_kernels", "torch"))
         ops.set_train_image(getattr(config, "image_kernels", "torch"))
         ops.set_train_optim(getattr(config, "optim_kernels", "torch"))
+        ops.set_train_head(getattr(config, "head_kernels", "torch"))
         torch.manual_seed(config.seed)
         self.rng = np.random.default_rng(config.seed)        # loss samples and find_corr subsamples
         Model = load_model(config.model)

@@ -1147,6 +1147,39 @@ int imf_fusion_train_backward(const float *dz, const float *x, int64_t n, const 
                               float *dtokens, float *const *grads /* host array [IMF_FT_NPARAM], entries may be NULL */,
                               int32_t *meta, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The descriptor head in training (csrc/head_train.hip) -------------------------------------------------------------
+ * Replaces: model/resunet.py:226-235 under autograd -- ME.cat(out, out_s1), conv1_tr (1x1, no bias), ReLU, final (1x1,
+ * bias) and the L2 normalisation -- by one forward and one backward call.  One shape: cu 64, cs 32, ch 64, co 32 (passed
+ * explicitly; anything else is IMF_EINVAL), 0 <= n <= 2^22.
+ *   u [n, cu], s [n, cs] row-major fp32 (the concatenation is never built; u's channels come first);  w1 [cu + cs, ch],
+ *   w2 [ch, co], bias [1, co]: the parameters' own layouts, nothing is packed.
+ *     H = relu(u w1[:cu] + s w1[cu:]);  Z = H w2 + bias;  r = sqrt(sum_c Z_c^2);  y = Z / r (normalize) or Z.
+ * forward: writes h [n, ch] (saved; doubles as the ReLU mask), y [n, co] and, with normalize, r [n] (else r may be NULL).
+ * backward: dy [n, co] -> dZ = (dy - y sum_c(dy y)) / r (normalize; else dZ = dy, y and r may be NULL), then
+ *     dbias = sum_rows dZ, dw2 = H^T dZ, dH = (dZ w2^T) [H > 0], dw1 = [u s]^T dH, du = dH w1[:cu]^T, ds = dH w1[cu:]^T.
+ *   du, ds, dw1, dw2 and dbias may each be NULL: that gradient, and whatever only it needs, is not computed; the bits of
+ *   the others do not change.  Every element of every non-NULL output is written.
+ * fp32 throughout.  Products run on the fp32 MFMA, K ascending; the two sums over a row's 32 channels are fixed shuffle
+ * trees; the three sums over rows are cut into chunks of imf_head_train_chunk_rows() rows, chunk partials added in chunk
+ * order in fp64 and rounded once.  No floating-point atomics: two calls give the same bits, and y, du and ds of a row
+ * depend on that row alone.  No epsilon: r == 0 gives what the division gives.
+ * meta: one int32 on the device, set to 0 by each call; IMF_HT_FLAG_NORM is raised when a row's r is 0 or not finite
+ *   (normalize only).  Neither call copies anything to the host or waits.
+ * n == 0: the forward writes nothing; the backward writes +0.0 into every non-NULL dw1, dw2 and dbias; no other pointer is
+ *   looked at.  IMF_EINVAL before any device call: other channel counts, n < 0 or > 2^22, a null required pointer, a short
+ *   workspace, u / s / w1 / w2 / dy / y / workspace not 16-byte aligned.  workspace (backward only):
+ *   imf_head_train_workspace_bytes(n) -- dZ, dH and the chunk partials; 0 for n < 1 or n > 2^22. */
+#define IMF_HT_FLAG_NORM 1
+int imf_head_train_chunk_rows(void);
+size_t imf_head_train_workspace_bytes(int64_t n);
+int imf_head_train_forward(const float *u, int cu, const float *s, int cs, int64_t n, const float *w1, int ch,
+                           const float *w2, int co, const float *bias, int normalize, float *h, float *r, float *y,
+                           int32_t *meta, void *stream);
+int imf_head_train_backward(const float *dy, const float *y, const float *r, const float *h, const float *u, int cu,
+                            const float *s, int cs, int64_t n, const float *w1, int ch, const float *w2, int co,
+                            int normalize, float *du, float *ds, float *dw1, float *dw2, float *dbias, void *workspace,
+                            size_t workspace_bytes, int32_t *meta, void *stream);
+
 /* ---- Descriptor Activation Mapping (csrc/dam.hip) ---------------------------------------------------------------------
  * Replaces: pytorch_dam/base_dam.py:120-173 + pytorch_dam/dam.py:15-21 -- 32 backward passes through the whole network per
  * target point, of which only final.kernel.grad is read -- by the closed form of that gradient, for T targets at once.

@@ -4,7 +4,8 @@ and imf_radius_pairs against scipy's cKDTree.
   decode     host decode of the batch's PLY files and images (sequential here; the trainer overlaps it on threads)
   geometry   random rotation, upload and first-occurrence voxelisation of every fragment of the batch
   pairs      radius_pairs (imf_radius_pairs) of every item at voxel x 1.5
-  forward    the two batched training-mode forwards (forward_layers; --fusion_kernels hip: csrc/fusion_train.hip)
+  forward    the two batched training-mode forwards (forward_layers; --fusion_kernels hip: csrc/fusion_train.hip,
+             --head_kernels hip: csrc/head_train.hip)
   loss       hardest-contrastive loss (sampling, two nn_search calls, masks; --loss_kernels hip: csrc/loss.hip)
   backward   loss.backward()
   step       optimizer.step() (--optim_kernels hip: one launch of csrc/optim.hip, which also leaves the weight images)
@@ -16,7 +17,8 @@ rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).quer
 (one thread) for the same sets.
 
 Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
-       [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--optim_kernels torch|hip] [--out FILE.json]
+       [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--optim_kernels torch|hip] [--head_kernels torch|hip]
+       [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -34,27 +36,10 @@ sys.path.insert(0, ROOT)
 from imfnet_amd import ops                                   # noqa: E402
 from imfnet_amd.matching import radius_pairs                 # noqa: E402
 from imfnet_amd.train.data import IndoorPairDataset          # noqa: E402
+from imfnet_amd.train.repro import SWITCHES, write_tree      # noqa: E402
 from imfnet_amd.train.trainer import HardestContrastiveTrainer, parse_config   # noqa: E402
 
-SWITCHES = ("norm_kernels", "loss_kernels", "fusion_kernels", "image_kernels", "optim_kernels")
 STAGES = ("decode", "geometry", "pairs", "forward", "loss", "backward", "step")
-
-
-def write_tree(root, clouds, images):
-    from PIL import Image
-    seq = os.path.join(root, "sceneA", "seq-01")
-    os.makedirs(seq)
-    for k in (0, 1):
-        pts = np.ascontiguousarray(clouds[k], dtype="<f4")
-        with open(os.path.join(seq, f"cloud_bin_{k}.ply"), "wb") as f:
-            f.write(b"ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\n"
-                    b"property float y\nproperty float z\nend_header\n" % len(pts))
-            f.write(pts.tobytes())
-        Image.fromarray((images[k] * 255).round().astype(np.uint8)).save(os.path.join(seq, f"cloud_bin_{k}_0.png"))
-    os.makedirs(os.path.join(root, "overlap"))
-    a, b = "sceneA/seq-01/cloud_bin_0.ply", "sceneA/seq-01/cloud_bin_1.ply"
-    with open(os.path.join(root, "overlap", "sceneA@seq-01-0.30.txt"), "w") as f:
-        f.write(f"{a} {b} 0.3\n{b} {a} 0.3\n")
 
 
 def voxel_reps(x, voxel):
