@@ -203,6 +203,9 @@ SIGNATURES = {
     "imf_bn_train_workspace_bytes": (_Z, [_L, _I]),
     "imf_bn_train_forward": (_I, [_P, _L, _I, _P, _P, _D, _P, _I, _P, _P, _D, _P, _P, _P, _Z, _P]),
     "imf_bn_train_backward": (_I, [_P, _P, _P, _I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "imf_in_workspace_bytes": (_Z, [_L, _I, _I]),
+    "imf_in_forward": (_I, [_P, _L, _I, _P, _I, _P, _P, _D, _P, _I, _P, _P, _P, _Z, _P]),
+    "imf_in_backward": (_I, [_P, _P, _P, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "imf_hc_loss_workspace_bytes": (_Z, [_L, _L, _I, _L, _L, _L, _L]),
     "imf_hc_loss_forward": (_I, [_P, _L, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _L, _D, _D, _P, _P, _P, _P, _P, _P, _P,
                                  _Z, _P]),

@@ -14,7 +14,9 @@ Everything stays on the GPU; the maps come from the coordinate manager's cache (
 
 `SparseBatchNormFunction` is the training-mode BatchNorm between them (csrc/norm_train.hip, ops.TRAIN_NORM == "hip"):
 fp64 batch statistics in a fixed order, the ReLU and the residual add of the residual block folded in, forward and
-backward; sparse.MinkowskiBatchNorm decides when it runs.
+backward; sparse.MinkowskiBatchNorm decides when it runs.  `SparseInstanceNormFunction` is the same for the InstanceNorm of
+the ResUNetIN2* residual blocks, the statistics cut per batch item over a device-side partition of the rows;
+sparse.MinkowskiInstanceNorm decides when it runs.
 
 `HardestContrastiveLossFunction` is the loss at the end (csrc/loss.hip, ops.TRAIN_LOSS == "hip"): both losses, the
 hardest negatives and the closed-form gradient with respect to the two feature matrices, fp64 sums in a fixed order;
@@ -233,6 +235,37 @@ class SparseBatchNormFunction(torch.autograd.Function):
         if need_r and not ctx.relu:
             dres = g
         return dx, dgamma, dbeta, dres, None, None
+
+
+class SparseInstanceNormFunction(torch.autograd.Function):
+    """y = [relu](instance_norm(x) [+ residual]) with per-item statistics (csrc/norm_train.hip, imf_in_*).  gamma / beta
+    are the module's [1, C] parameters; item_starts is the int32 [n_items + 1] device array of the rows' partition."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, item_starts, relu):
+        from .sparse import MinkowskiInstanceNorm
+        xc = x.detach().contiguous()
+        res = None if residual is None else residual.detach().contiguous()
+        y, stats = ops.in_forward(xc, item_starts, gamma.detach().reshape(-1).contiguous(),
+                                  beta.detach().reshape(-1).contiguous(), MinkowskiInstanceNorm.EPS, res, relu)
+        ctx.save_for_backward(xc, y, stats, gamma, item_starts)
+        ctx.relu = bool(relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y, stats, gamma, item_starts = ctx.saved_tensors
+        need_x, need_g, need_b, need_r = ctx.needs_input_grad[:4]
+        g = grad_out.contiguous().float()
+        if not (need_x or need_g or need_b or need_r):
+            return None, None, None, None, None, None
+        # without a ReLU the residual's gradient is the incoming gradient itself: no copy
+        dx, dgamma, dbeta, dres = ops.in_backward(g, x, y, stats, gamma.detach().reshape(-1).contiguous(), item_starts,
+                                                  ctx.relu, need_x, need_g, need_b, need_r and ctx.relu)
+        if need_r and not ctx.relu:
+            dres = g
+        return (dx, None if dgamma is None else dgamma.view_as(gamma), None if dbeta is None else dbeta.view_as(gamma),
+                dres, None, None)
 
 
 class HardestContrastiveLossFunction(torch.autograd.Function):

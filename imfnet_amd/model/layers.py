@@ -38,16 +38,11 @@ class BasicBlockBase(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        if isinstance(self.norm1, ME.MinkowskiBatchNorm):
-            # norm1 -> relu and norm2 -> + x -> relu, each ONE call: the same torch ops in the same order as below with
-            # ops.TRAIN_NORM == "torch", one HIP op each (csrc/norm_train.hip) with "hip" in training mode
-            y = self.conv2(self.norm1.forward_fused(self.conv1(x), relu=True))
-            return self.norm2.forward_fused(y, residual=x if self.downsample is None else self.downsample(x), relu=True)
-        relu = ME.MinkowskiFunctional.relu
-        y = relu(self.norm1(self.conv1(x)))
-        y = self.norm2(self.conv2(y))
-        y += x if self.downsample is None else self.downsample(x)
-        return relu(y)
+        # norm1 -> relu and norm2 -> + x -> relu, each ONE call, for both norms: with ops.TRAIN_NORM == "torch" the torch ops
+        # in the order norm, add, relu; with "hip" one HIP op each (csrc/norm_train.hip) -- BatchNorm in training mode,
+        # InstanceNorm always
+        y = self.conv2(self.norm1.forward_fused(self.conv1(x), relu=True))
+        return self.norm2.forward_fused(y, residual=x if self.downsample is None else self.downsample(x), relu=True)
 
     def fused(self, x, bn1, bn2):
         """x: SparseTensor; bn1 / bn2: folded eval-BatchNorm (scale, shift) pairs."""

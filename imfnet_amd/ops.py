@@ -730,6 +730,11 @@ def fusion_attention(x, kt_packed, v_packed, n_tokens, tokens_padded, fw, out=No
 #   "hip"             = csrc/norm_train.hip through autograd.SparseBatchNormFunction: fp64 statistics in a fixed order,
 #                       ReLU and residual add folded in, bit-reproducible.  Used only in training mode under autograd on
 #                       fp32 GPU features with affine parameters; every other call runs the torch ops whatever the switch.
+# The same switch covers the InstanceNorm of the ResUNetIN2* residual blocks (sparse.MinkowskiInstanceNorm):
+#   "torch" (default) = the torch ops it always ran (index_add_ sums, one host wait per call), then the add, then F.relu;
+#   "hip"             = the imf_in_* calls of csrc/norm_train.hip through autograd.SparseInstanceNormFunction, in training,
+#                       eval and no_grad alike (InstanceNorm is the same function in all three), on fp32 GPU rows whose
+#                       coordinate manager knows the item partition; every other call runs the torch ops.
 TRAIN_NORM_CHOICES = ("torch", "hip")
 TRAIN_NORM = os.environ.get("IMF_TRAIN_NORM", "torch")
 if TRAIN_NORM not in TRAIN_NORM_CHOICES:
@@ -800,6 +805,70 @@ def bn_train_backward(dy, x, y, stats, gamma, relu=False, want_dx=True, want_dga
     check(_lib.lib().imf_bn_train_backward(dy.data_ptr(), x.data_ptr(), _ptr(y), int(bool(relu)), stats.data_ptr(),
                                            gamma.data_ptr(), n, c, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dres),
                                            ws.data_ptr(), nbytes, _stream()), "imf_bn_train_backward")
+    return dx, dgamma, dbeta, dres
+
+
+def item_starts_tensor(items, device):
+    """The host-side [(first row, rows)] of a level's batch items as the int32 [n_items + 1] device array the InstanceNorm
+    calls take: one small upload, nothing waits for the device."""
+    return torch.tensor([s for s, _ in items] + [items[-1][0] + items[-1][1]], dtype=torch.int32, device=device)
+
+
+def _in_args(x, item_starts, name):
+    _req(x, torch.float32, name, 2)
+    n, c = x.shape
+    if _req(item_starts, torch.int32, "item_starts", 1).device != x.device:
+        raise ImfError(f"item_starts is on {item_starts.device}, {name} on {x.device}")
+    n_items = item_starts.shape[0] - 1
+    if not 1 <= n_items <= _lib.MAX_BATCH:
+        raise ImfError(f"item_starts must be [n_items + 1] with 1 <= n_items <= {_lib.MAX_BATCH}, got {tuple(item_starts.shape)}")
+    if n < 1:
+        raise ImfError(f"{name} must have at least one row")
+    return n, c, n_items
+
+
+def _in_workspace(n, c, n_items, device):
+    nbytes = _lib.lib().imf_in_workspace_bytes(n, c, n_items)
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device), nbytes
+
+
+def in_forward(x, item_starts, gamma, beta, eps, residual=None, relu=False):
+    """imf_in_forward: (y [N, C] fp32, stats [n_items, 2C] fp64 = per item the mean and 1 / sqrt(biased variance + eps)).
+    item_starts: int32 [n_items + 1] on the device, item b = rows [item_starts[b], item_starts[b + 1]); never read here."""
+    n, c, n_items = _in_args(x, item_starts, "x")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if _req(t, torch.float32, name, 1).shape[0] != c:
+            raise ImfError(f"{name} must be [{c}]")
+    if residual is not None:
+        _bn_rows(residual, "residual", n, c)
+    y = torch.empty_like(x)
+    stats = torch.empty((n_items, 2 * c), dtype=torch.float64, device=x.device)
+    ws, nbytes = _in_workspace(n, c, n_items, x.device)
+    check(_lib.lib().imf_in_forward(x.data_ptr(), n, c, item_starts.data_ptr(), n_items, gamma.data_ptr(), beta.data_ptr(),
+                                    float(eps), _ptr(residual), int(bool(relu)), y.data_ptr(), stats.data_ptr(),
+                                    ws.data_ptr(), nbytes, _stream()), "imf_in_forward")
+    return y, stats
+
+
+def in_backward(dy, x, y, stats, gamma, item_starts, relu=False, want_dx=True, want_dgamma=True, want_dbeta=True,
+                want_dresidual=False):
+    """imf_in_backward: (dx, dgamma, dbeta, dresidual), None for each output that is not wanted.  y is read only for the
+    ReLU mask y > 0 (may be None when relu is false)."""
+    n, c, n_items = _in_args(dy, item_starts, "dy")
+    _bn_rows(x, "x", n, c)
+    if relu or y is not None:
+        _bn_rows(y, "y", n, c)
+    if tuple(_req(stats, torch.float64, "stats", 2).shape) != (n_items, 2 * c) or \
+            _req(gamma, torch.float32, "gamma", 1).shape[0] != c:
+        raise ImfError(f"stats must be [{n_items}, {2 * c}] and gamma [{c}]")
+    dx = torch.empty_like(x) if want_dx else None
+    dgamma = torch.empty_like(gamma) if want_dgamma else None
+    dbeta = torch.empty_like(gamma) if want_dbeta else None
+    dres = torch.empty_like(x) if want_dresidual else None
+    ws, nbytes = _in_workspace(n, c, n_items, x.device)
+    check(_lib.lib().imf_in_backward(dy.data_ptr(), x.data_ptr(), _ptr(y), int(bool(relu)), stats.data_ptr(),
+                                     gamma.data_ptr(), item_starts.data_ptr(), n, c, n_items, _ptr(dx), _ptr(dgamma),
+                                     _ptr(dbeta), _ptr(dres), ws.data_ptr(), nbytes, _stream()), "imf_in_backward")
     return dx, dgamma, dbeta, dres
 
 

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from ._lib import ImfError
+from ._lib import MAX_BATCH, ImfError
 
 
 class CoordinateMapKey:
@@ -57,6 +57,28 @@ class CoordinateManager:
         self._rulebooks = {}
         self.meta = meta              # optional shared [n_levels,2] count block (row 0 = level0)
         self.meta_used = 1
+        self.n_items = None           # batch items, when level 0's rows are known to be grouped by ascending batch index
+        self._item_starts = {}
+
+    def item_starts(self, ts, n_rows):
+        """int32 [n_items + 1] on the device: item b owns rows [s[b], s[b + 1]) of the level at tensor stride `ts`; None
+        when the rows are not known to be grouped by item (or the level does not have `n_rows` rows).  Built once per
+        level without waiting for the device: from the (first row, rows) pairs a batched pyramid keeps on the host
+        (ops.PyramidFuture.result), or by a search over the batch column when `n_items` is known -- the compaction behind
+        every coarser level keeps the rows' order, so a level-0 map grouped by item stays grouped at every stride."""
+        lv = self.levels.get(ts)
+        if lv is None or lv.n is None or lv.n != n_rows:
+            return None
+        if ts not in self._item_starts:
+            items = getattr(lv, "items", None)
+            if items is not None:
+                ok = 1 <= len(items) <= MAX_BATCH and sum(cnt for _, cnt in items) == lv.n
+                self._item_starts[ts] = ops.item_starts_tensor(items, lv.device) if ok else None
+            elif self.n_items is not None:
+                self._item_starts[ts] = ops.fusion_item_starts(lv.coords[:, 0], self.n_items)
+            else:
+                self._item_starts[ts] = None
+        return self._item_starts[ts]
 
     # -- levels ---------------------------------------------------------------------------------
     def build_pyramid(self, max_stride=8, before_sync=None):
@@ -144,11 +166,21 @@ class SparseTensor:
                 raise ValueError("features and coordinates must have the same number of rows")
             coordinates = coordinates.to(device=device, dtype=torch.int32).contiguous()
             level0 = ops.level_from_coords(coordinates)
+            batch = coordinates[:, 0]
+            probe = None if batch.numel() == 0 or ops.TRAIN_NORM != "hip" else \
+                torch.stack([(batch[1:] >= batch[:-1]).all().to(torch.int32), batch.min(), batch.max()])
             ops.sync_levels([level0])
             if level0.n != coordinates.shape[0]:
                 # util/misc.py never hits this: sparse_quantize already made the rows unique
                 raise ImfError("duplicate coordinates: quantise with utils.sparse_quantize first")
             coordinate_manager = CoordinateManager(level0)
+            if probe is not None:
+                # ops.TRAIN_NORM == "hip" at construction: whether the rows are grouped by item, read here, where the host
+                # waits for the row count anyway, so that MinkowskiInstanceNorm never asks the device again.  A tensor
+                # built while the switch was "torch" keeps n_items None and its InstanceNorms stay on the torch ops.
+                ascending, b_min, b_max = probe.cpu().tolist()
+                if ascending and b_min >= 0 and b_max < MAX_BATCH:
+                    coordinate_manager.n_items = b_max + 1
             coordinate_map_key = CoordinateMapKey(tensor_stride)
         elif coordinate_manager is None or coordinate_map_key is None:
             raise ValueError("SparseTensor needs coordinates or (coordinate_map_key, coordinate_manager)")
@@ -354,8 +386,11 @@ class MinkowskiBatchNorm(nn.Module):
 class MinkowskiInstanceNorm(nn.Module):
     """ME.MinkowskiInstanceNorm (the `IN` blocks of ResUNetIN2*, model/common.py:7-8): per batch item and channel,
     (x - mean) / sqrt(var + 1e-8) over that item's rows (biased variance: ME computes both with a global average pooling),
-    then weight * x + bias with [1, C] parameters.  Plain torch on the rows -- these variants are not the checkpoint's
-    (ResUNetBN2C) and take the per-layer path, not the fused plan.  [ME 0.5.4 conventions RECALLED: eps, biased variance.]"""
+    then weight * x + bias with [1, C] parameters.  These variants are not the checkpoint's (ResUNetBN2C) and take the
+    per-layer path, not the fused plan.  [ME 0.5.4 conventions RECALLED: eps, biased variance.]
+    By default plain torch on the rows (index_add_ sums and one host wait per call).  With ops.TRAIN_NORM == "hip" the
+    imf_in_* kernels of csrc/norm_train.hip instead, the block's ReLU and residual add folded in (`forward_fused`): fp64
+    statistics per item in a fixed order, no host wait, bit-reproducible, forward and backward."""
 
     EPS = 1e-8
 
@@ -365,7 +400,40 @@ class MinkowskiInstanceNorm(nn.Module):
         self.bias = nn.Parameter(torch.zeros(1, num_features))
 
     def forward(self, x):
+        return self.forward_fused(x)
+
+    def _hip_item_starts(self, x, f):
+        """The rows' item partition (int32 [n_items + 1] on the device) when this call runs on the imf_in_* kernels of
+        csrc/norm_train.hip, else None: the switch, fp32 GPU rows and parameters, and a coordinate manager that knows the
+        partition of this map without asking the device (CoordinateManager.item_starts)."""
+        if ops.TRAIN_NORM != "hip" or not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 and f.dim() == 2):
+            return None
+        cm, key = getattr(x, "coordinate_manager", None), getattr(x, "coordinate_map_key", None)
+        if not isinstance(cm, CoordinateManager) or key is None or f.shape[0] == 0:
+            return None
+        if not all(p.is_cuda and p.dtype == torch.float32 for p in (self.weight, self.bias)):
+            return None
+        return cm.item_starts(key.tensor_stride, f.shape[0])
+
+    def forward_fused(self, x, residual=None, relu=False):
+        """relu(instance_norm(x) + residual), the residual (a SparseTensor on x's map, or its feature matrix) and the ReLU
+        optional.  With ops.TRAIN_NORM == "hip", one HIP op in training, eval and no_grad alike (`_hip_item_starts`: no host
+        wait, no floating-point atomics).  In every other case the torch ops in the order the residual block always issued
+        them: norm, then add, then relu."""
         f = x.F
+        res = residual if residual is None or torch.is_tensor(residual) else residual.F
+        starts = self._hip_item_starts(x, f)
+        if starts is not None:
+            from .autograd import SparseInstanceNormFunction
+            return x._like(SparseInstanceNormFunction.apply(f, self.weight, self.bias, res, starts, bool(relu)))
+        out = self._torch_norm(x, f)
+        if res is not None:
+            out = out + res
+        if relu:
+            out = F.relu(out)
+        return x._like(out)
+
+    def _torch_norm(self, x, f):
         item = x.C[:, 0].long()
         n_items = int(item.max().item()) + 1 if item.numel() else 0
         if n_items <= 1:
@@ -380,7 +448,7 @@ class MinkowskiInstanceNorm(nn.Module):
             cen = f - mean[item]
             var = torch.zeros_like(mean).index_add_(0, item, cen * cen) / cnt
             out = cen * torch.rsqrt(var + self.EPS)[item]
-        return x._like(out * self.weight + self.bias)
+        return out * self.weight + self.bias
 
 
 class MinkowskiFunctional:

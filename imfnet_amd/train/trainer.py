@@ -109,8 +109,9 @@ def make_parser():
     a("--image_H", type=int, default=120)
     a("--seed", type=int, default=0)
     a("--norm_kernels", type=str, default="torch", choices=("torch", "hip"),
-      help="training-mode BatchNorm of the sparse path: torch ops, or the fused deterministic HIP kernels "
-           "(fp64 statistics, ReLU and residual add folded in)")
+      help="the norms of the sparse path -- training-mode BatchNorm, and the InstanceNorm of the ResUNetIN2* residual "
+           "blocks --: torch ops, or the fused deterministic HIP kernels (fp64 statistics in a fixed order, ReLU and "
+           "residual add folded in, no host wait)")
     a("--loss_kernels", type=str, default="torch", choices=("torch", "hip"),
       help="the hardest-contrastive loss and its gradient: torch ops, or the deterministic HIP kernels "
            "(fp64 terms in a fixed order, no host wait)")

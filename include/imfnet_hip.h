@@ -1053,6 +1053,46 @@ int imf_bn_train_backward(const float *dy, const float *x, const float *y, int r
                           const float *gamma, int64_t n, int c, float *dx, float *dgamma, float *dbeta, float *dresidual,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- InstanceNorm of the sparse path (csrc/norm_train.hip) -------------------------------------------------------------
+ * Replaces: ME.MinkowskiInstanceNorm inside the residual blocks of the ResUNetIN2* variants (model/common.py:7-8) and the
+ * ReLU / residual add that follow it, forward and backward: the imf_bn_train_* arithmetic with the statistics cut per
+ * batch item.  Rows are grouped by item: item b owns rows [item_starts[b], item_starts[b + 1]) of the row-major fp32
+ * [n, c] matrices; item_starts is int32 [n_items + 1] ON THE DEVICE and no call reads it on the host (the kernels clamp
+ * its values to a non-decreasing sequence inside [0, n], so no content of it makes them leave the matrices; rows before
+ * item_starts[0] or from item_starts[n_items] on belong to no item and are not written).  1 <= n_items <= IMF_MAX_BATCH,
+ * 1 <= n < 2^31, any c >= 1, 16-byte vectors when c % 4 == 0 and the pointers are 16-byte aligned.
+ * Summation order: every item is cut into chunks of imf_bn_train_chunk_rows() rows (the constant of the BatchNorm calls)
+ * counted from the item's OWN first row, and one workgroup per item adds that item's chunk partials in chunk order.  The
+ * bits of item b's rows of y and dx therefore depend on item b's rows alone: not on the item's place in the batch, the
+ * other items, the grid or the CU count.  No floating-point atomics, no workgroup waits for another, two calls give the
+ * same bits.  Every call takes a stream and synchronises nothing; bad arguments (n < 1, c < 1, n_items outside
+ * 1 .. IMF_MAX_BATCH, a short workspace, a null required pointer) return IMF_EINVAL before any launch.
+ * workspace: imf_in_workspace_bytes(n, c, n_items), 8-byte aligned, for either call (0 for arguments a call refuses).
+ *
+ * forward:  stats[b][0..c) = mean of item b, stats[b][c..2c) = 1 / sqrt(biased variance + eps), both fp64, from fp64 sums
+ *           of d = x - p and d^2 about the pivot p = the item's first row (as the BatchNorm call: no cancellation when
+ *           |mean| >> sigma);  xh = fp32((double(x) - mean_b) * rstd_b);  y = fmaf(xh, gamma, beta) (+ residual) (then
+ *           ReLU when relu != 0).  An item of one row has variance 0: xh = 0 and y = beta (+ residual).  An item without
+ *           rows writes no row (its stats are 0, 0).  No running statistics.
+ *           Per element  |y - exact| <= 4 * 2^-24 * (|gamma xh| + |beta| + |residual|)
+ *                                       + |gamma| * rstd_b * 2^-53 * (n_b * max_b |x - p| + 2 |mean_b|).
+ *           The first term is the BatchNorm call's (the three fp32 roundings).  The second is what the fp64 statistics'
+ *           own rounding moves xh by -- n_b additions of |d| <= max |x - p| behind sum d, then the addition of n_b p and
+ *           the division, each on |mean_b| --: it is multiplied by rstd, which eps = 1e-8 lets reach 1e4 where BatchNorm's
+ *           1e-5 stops it at 316 and the first term covered it.  With n_b <= 600, |x| <= 12 and rstd <= 2 it is below
+ *           2^-39 |gamma|; a channel that is constant inside an item has d = 0 everywhere, mean = p exactly and xh = 0.
+ * backward: g = dy, or 0 where relu != 0 and not y > 0;  per item S1_b = sum_b g, S2_b = sum_b g * xh;
+ *           dx = gamma * rstd_b * (g - S1_b / n_b - xh * S2_b / n_b);  dbeta = sum_b S1_b and dgamma = sum_b S2_b, the
+ *           items added in item order;  dresidual = g.  fp64 up to each fp32 store.  dx, dgamma, dbeta and dresidual
+ *           may each be NULL exactly as in imf_bn_train_backward; y may be NULL when relu == 0. */
+size_t imf_in_workspace_bytes(int64_t n, int c, int n_items);
+int imf_in_forward(const float *x, int64_t n, int c, const int32_t *item_starts /* device [n_items + 1] */, int n_items,
+                   const float *gamma, const float *beta, double eps, const float *residual /* or NULL */, int relu,
+                   float *y, double *stats /* [n_items][2c] */, void *workspace, size_t workspace_bytes, void *stream);
+int imf_in_backward(const float *dy, const float *x, const float *y, int relu, const double *stats, const float *gamma,
+                    const int32_t *item_starts, int64_t n, int c, int n_items, float *dx, float *dgamma, float *dbeta,
+                    float *dresidual, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- The hardest-contrastive loss of training (csrc/loss.hip) -----------------------------------------------------------
  * Replaces: lib/trainer.py:440-493 `contrastive_hardest_negative_loss` and torch's autograd of it (row gathers whose
  * backward is an atomic index_put, two sort-based isin calls, boolean-mask indexing that waits for the device).

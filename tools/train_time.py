@@ -18,7 +18,7 @@ rigid motion, r = 3.75 cm, with the pair count; cpu_ckdtree is cKDTree(dst).quer
 
 Usage: python tools/train_time.py [--iters 10] [--warmup 3] [--batch 2] [--norm_kernels torch|hip] [--loss_kernels torch|hip]
        [--fusion_kernels torch|hip] [--image_kernels torch|hip] [--optim_kernels torch|hip] [--head_kernels torch|hip]
-       [--out FILE.json]
+       [--model ResUNetIN2C] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import json
@@ -73,6 +73,7 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     for s in SWITCHES:
         ap.add_argument("--" + s, default="torch", choices=("torch", "hip"))
+    ap.add_argument("--model", default=None, help="the trainer's --model (default: the trainer's own, ResUNetBN2C)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
@@ -84,7 +85,8 @@ def main():
         write_tree(root, clouds, images)
         cfg = parse_config(["--threed_match_dir", root, "--overlap_path", os.path.join(root, "overlap"),
                             "--batch_size", str(a.batch), "--out_dir", os.path.join(root, "out")] +
-                           [v for s in SWITCHES for v in ("--" + s, getattr(a, s))])
+                           [v for s in SWITCHES for v in ("--" + s, getattr(a, s))] +
+                           (["--model", a.model] if a.model else []))
         ds = IndoorPairDataset("train", ["sceneA"], cfg, seed=0)
         tr = HardestContrastiveTrainer(cfg, ds, None)
         rows, n_vox, n_pairs = [], [], []
@@ -105,6 +107,7 @@ def main():
         res[k] = float(np.median([r.get(k, 0.0) for r in rows])) * 1e3
     res["iteration"] = float(np.median([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
     res.update({s: getattr(a, s) for s in SWITCHES})
+    res["model"] = cfg.model
     res["iteration_spread"] = float(np.ptp([sum(r.get(k, 0.0) for k in STAGES) for r in rows])) * 1e3
     res.update(batch=a.batch, voxels=n_vox, positive_pairs=n_pairs, rotation=True, scale=False)
     T = np.eye(4)
