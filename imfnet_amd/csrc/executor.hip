@@ -247,8 +247,9 @@ int validate(const imf_resunet_desc *net, const imf_resunet_io *io, const Layout
               io->float_arena_bytes, l.float_bytes);
   const int n_events = io->pyramid ? 9 : 10;   // (the occupancy-sorted twins have their own joins: up to three)
   for (int i = 0; i < n_events; ++i) IMF_REQUIRE(io->events[i], "imf_resunet_forward: events[%d] missing", i);
-  for (int i = 0; i < NBUF; ++i)   // variant 6 reads its inputs through a 2 GiB buffer window
-    IMF_REQUIRE(l.buf_floats[i] * sizeof(float) < (1ull << 31), "imf_resunet_forward: feature buffer %d exceeds 2 GiB", i);
+  for (int i = 0; i < NBUF; ++i)   // the LDS-DMA kernels gather their input rows through a window of IMF_CONV_ROW_WINDOW bytes
+    IMF_REQUIRE(l.buf_floats[i] * sizeof(float) <= (size_t)IMF_CONV_ROW_WINDOW,
+                "imf_resunet_forward: feature buffer %d exceeds the convolutions' row window (2 GiB - 4 KiB)", i);
   return IMF_OK;
 }
 

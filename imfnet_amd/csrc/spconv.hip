@@ -362,7 +362,7 @@ int imf_spconv_fwd(const imf_conv_args *a, void *stream) {
   const bool simple = !v16 && (a->variant == 1 || a->kvol >= kKCache || (a->c_b > 0 && a->c_a % (16 * J) != 0));
   // Variant 0 (fp32 MFMA) runs on the LDS-DMA kernels too (k_spconv_g / k_spconv_w with AR = kArF32: the fp32 weight image
   // has the split-f16 image's sub-stage addressing) wherever their tables cover the shape; IMF_TAG_REGS keeps the
-  // register-staged kernel k_spconv_mfma (A/B, inputs beyond the 2 GiB buffer window).
+  // register-staged kernel k_spconv_mfma (A/B, inputs beyond IMF_CONV_ROW_WINDOW: the caller's choice, the library sees no sizes).
   const bool dma0 = a->variant == 0 && !simple && !regs && a->kvol * (cin / 32) < kSubTab && a->c_a <= 1024 && a->c_b <= 1024;
   const bool dma = v16 || dma0;
   // the wave-split kernel (spconv_w.hip): the whole unit of rows in one workgroup, no split-K partitions, no reduce launch

@@ -25,7 +25,7 @@
 // (checked on the hardware by the micro-benchmark).  Everything lives in ONE __shared__ array: with a second
 // object hipcc 7.2 drains the DMA queue before every ds_read.
 //
-// Not covered here: inputs beyond the 2 GiB buffer window -- variant 0's register-staged k_spconv_mfma (spconv.hip) serves them.
+// Not covered here: inputs beyond the row window (IMF_CONV_ROW_WINDOW = 0x7FFFF000 bytes, the descriptors below) -- variant 0's register-staged k_spconv_mfma (spconv.hip) serves them.
 #include "spconv_shared.h"
 
 #ifndef IMF_G_ABL

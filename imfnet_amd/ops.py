@@ -458,6 +458,7 @@ def conv_kernel_name(variant, cin, cout, staging=None, kernel_tag=0):
 
 
 FMT_A_SPLIT, FMT_RES_SPLIT, FMT_OUT_SPLIT = 1, 2, 4      # imf_conv_args.operand_format (include/imfnet_hip.h)
+CONV_ROW_WINDOW = 0x7FFFF000                             # IMF_CONV_ROW_WINDOW: bytes of an input the LDS-DMA kernels can gather from
 
 
 def to_operand_image(x):
@@ -523,9 +524,11 @@ def spconv(in_a, w_packed, cout, rb, in_b=None, scale=None, shift=None, residual
     if n_out_dev is not None:
         _req(n_out_dev, torch.int32, "n_out_dev", 1)
         a.n_out_dev, a.slots_extra = n_out_dev.data_ptr(), int(slots_extra)
-    big = max(in_a.numel(), 0 if in_b is None else in_b.numel()) * 4 >= 2 ** 31
+    # IMF_CONV_ROW_WINDOW: the LDS-DMA kernels read a row whose bytes lie at or beyond this offset as zeros, silently
+    big = max(in_a.numel(), 0 if in_b is None else in_b.numel()) * 4 > CONV_ROW_WINDOW
     if variant in (6, 3) and big:
-        raise ImfError("variants 6 / 3 address their inputs through a 2 GiB buffer window: use variant 0 for larger matrices")
+        raise ImfError("variants 6 / 3 address their inputs through a buffer window of 0x7FFFF000 bytes (2 GiB - 4 KiB): "
+                       "use variant 0 for larger matrices")
     if variant == 0 and big:
         a.kernel_tag = _lib.TAG_REGS                      # the LDS-DMA kernels share that window: the register-staged kernel
     need = (L.imf_packed_weight_floats_split16 if variant == 6 else L.imf_packed_weight_floats_bf16x3 if variant == 3

@@ -157,6 +157,12 @@ int imf_pyramid_build_dyn(const void *xyz, int xyz_is_f64, const int32_t *dyn, i
  *                                        row through kernel offset k, -1 = none
  *   tile_mask uint32[n_tiles * 4]        bit k set <=> some row of the tile has an input at offset k
  * Kernel offset order: k = (dx+r) + K1*(dy+r) + K1^2*(dz+r), x fastest (ME kernel_region.hpp).
+ * PRECONDITION of imf_spconv_fwd: every tile that holds a live row (tile_rows >= 0) has at least one active offset.  A
+ * tile whose mask is 0 is padding to the convolution kernels: an unsplit launch skips it whole and writes none of its rows
+ * (a split launch would write epilogue(0) for them through the reduce kernel, a 48-row unit that shares rows with an active
+ * tile writes its part; do not rely on any of it).  Every map builder
+ * of this library meets it -- an output row always has its centre, a parent or a child.  A live row WITHOUT input inside a
+ * tile that has an active offset is fine and is written as epilogue(0).
  * ---------------------------------------------------------------------------------------------- */
 
 /* Identity slot order (slot == output row), padded to a whole tile. */
@@ -249,7 +255,9 @@ typedef struct imf_conv_args {
   int32_t kvol, cout;
   const int32_t *tile_rows;         /* NULL = identity (slot == row)                                  */
   const int32_t *nbr;               /* NULL allowed when kvol == 1: input row == output row           */
-  const uint32_t *tile_mask;        /* NULL allowed when kvol == 1: every tile active at offset 0     */
+  const uint32_t *tile_mask;        /* NULL allowed when kvol == 1: every tile active at offset 0.  A tile with mask 0 is
+                                       skipped whole by unsplit launches, so a tile that holds a live row must have an
+                                       active offset (the rulebook's precondition, above)              */
   int64_t n_slots, n_out;
   const float *scale;     /* [cout] or NULL   y = acc * scale + shift  (folded eval BatchNorm /   */
   const float *shift;     /* [cout] or NULL                             bias)                     */
@@ -260,18 +268,24 @@ typedef struct imf_conv_args {
   int32_t split_k;        /* 0 = choose automatically; >= 1 = number of kernel-offset partitions  */
   int32_t variant;        /* 0 = fp32 MFMA (v_mfma_f32_16x16x4_f32: the reference's arithmetic), since round 5 on the LDS-DMA
                                  kernels k_spconv_g / k_spconv_w (AR = kArF32) wherever their tables cover the shape
-                                 (kvol <= 27, kvol * cin / 32 < 224, <= 1024 channels per source, inputs < 2 GiB), else --
+                                 (kvol <= 27, kvol * cin / 32 < 224, <= 1024 channels per source, inputs within the row window below), else --
                                  or with IMF_TAG_REGS -- on the register-staged k_spconv_mfma;
                              1 = the same arithmetic without any pipeline (simple reference kernel; any kvol);
                              2, 4, 5 = retired round-1 experiments (their measurements: DESIGN.md 4), IMF_EINVAL;
                              3 = "bf16x3": fp32 operands carried exactly by three bf16 parts each, six
                                  v_mfma_f32_16x16x32_bf16 per 32 channels, fp32 accumulation (w_packed from
                                  imf_pack_weights_bf16x3; fp32 rows in, fp32 rows out, no range restriction; kvol <= 27;
-                                 in_a / in_b smaller than 2 GiB each).  k_spconv_g / k_spconv_w with AR = kArBf16x3;
+                                 in_a / in_b at most IMF_CONV_ROW_WINDOW bytes each).  k_spconv_g / k_spconv_w with AR = kArBf16x3;
                              6 = fp32-class arithmetic on the f16 matrix pipe with split operands, both operands staged
                                  global -> LDS by DMA (k_spconv_g / k_spconv_w)
                                  (w_packed from imf_pack_weights_split16; kvol <= 27; |input| < 65504;
-                                 in_a / in_b smaller than 2 GiB each: raw-buffer addressing) */
+                                 in_a / in_b at most IMF_CONV_ROW_WINDOW bytes each: raw-buffer addressing).
+                             THE ROW WINDOW.  k_spconv_g and k_spconv_w (variants 6 and 3 always, variant 0 without
+                             IMF_TAG_REGS) gather input rows through buffer descriptors of IMF_CONV_ROW_WINDOW =
+                             0x7FFFF000 bytes (2 GiB - 4 KiB: the `no input` row index then lies outside for every row
+                             stride).  A row whose bytes lie at or beyond that offset of in_a / in_b is read as ZEROS,
+                             without an error -- the library sees pointers, not sizes, so the CALLER keeps each source
+                             within the window, or passes variant 0 with IMF_TAG_REGS (plain loads, any size) */
   void *workspace;        /* split-K partial sums (NULL allowed iff split_k resolves to 1) */
   size_t workspace_bytes; /* >= imf_spconv_workspace_bytes(n_slots, cout, split)                  */
   void *ev_begin, *ev_end; /* optional hipEvent_t pair recorded on `stream` immediately around the
@@ -301,6 +315,7 @@ typedef struct imf_conv_args {
                              its consumers the conversions (same products bit for bit).  A residual read takes hi + lo,
                              i.e. the value to 22 significant bits (relative 2^-22). */
 } imf_conv_args;
+#define IMF_CONV_ROW_WINDOW 0x7FFFF000ll   /* bytes of in_a / in_b the LDS-DMA kernels can gather rows from (imf_conv_args.variant) */
 /* imf_conv_args.kernel_tag (variants 6, 3 and 0): which kernel and which workgroup shape a launch takes.  The values are
  * part of the ABI (trace records and C callers carry them as integers).  Bits that do not apply to a launch's arithmetic
  * are ignored (csrc/spconv_w.hip, w_build_of, says which).  Whatever the bits, a row's sums depend on the wavefront
@@ -308,7 +323,7 @@ typedef struct imf_conv_args {
 #define IMF_TAG_LABEL   1   /* profiling label: the identical kernel under a second symbol (k_spconv_g<.., 1>, whole-tile
                                k_spconv_w of 8 wavefronts: the image branch's dense convolutions) */
 #define IMF_TAG_REGS    2   /* variant 0: the register-staged fp32 kernel k_spconv_mfma (the one that serves inputs beyond
-                               the 2 GiB buffer window); variants 6 / 3: IMF_EUNSUPPORTED / IMF_EINVAL */
+                               IMF_CONV_ROW_WINDOW); variants 6 / 3: IMF_EUNSUPPORTED / IMF_EINVAL */
 #define IMF_TAG_WAVE8   4   /* the wave-split kernel k_spconv_w (csrc/spconv_w.hip) with 8 wavefronts per workgroup ... */
 #define IMF_TAG_WAVE4   8   /* ... or with 4 (WAVE8 wins when both are set) -- for levels of a few hundred 64-row tiles or
                                fewer: one workgroup owns a (unit of rows, 64-column slab) for all kernel offsets, its

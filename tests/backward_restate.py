@@ -10,7 +10,8 @@ Integer data (features in [-3, 3], weights in [-2, 2], gradients in [-3, 3], sto
 partial sum is an integer far below 2^24, so ANY correct fp32-accumulating kernel returns exactly the integers float64
 returns here, in any summation order and in any of the three arithmetics (bf16x3 and split-f16 carry such operands in their
 first part).  The comparison is torch.equal; one missing, duplicated or misrouted pair changes the result.  A power-of-two
-scale of an operand is an exponent shift and keeps all of it exact.
+scale of an operand is an exponent shift and keeps all of it exact.  Operands whose LATER parts carry bits (the f16 lo
+half, bf16x3's second and third part) and still sum exactly: the generators of tests/spconv_cases.py.
 
 Kernel maps come in two shapes: the oracle's `nbr [n_out, K]` (row of the input per output row and offset, -1 = none) and
 the library's tiled one (`tile_rows [n_slots]` = output row of every slot, -1 = padding; `nbr [K, n_slots]`), see
