@@ -280,6 +280,7 @@ SIGNATURES = {
                                       C.POINTER(FusionWeights), C.c_float, _P, _P, _Z, _P]),
     "imf_fusion_attention_dyn_v": (_I, [_P, _L, _P, _P, _I, _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I,
                                         C.POINTER(FusionWeights), C.c_float, _P, _P, _Z, _I, _P]),
+    "imf_host_rigid_fit": (_I, [_P, _P, _I, _P]),
     "imf_ransac_workspace_bytes": (_Z, [_I]),
     "imf_ransac_registration": (_I, [_P, _L, _P, _L, _P, _I, _D, _D, _I, C.c_uint64, _P, _P, _P, _P, _Z, _P]),
     "imf_gather_points": (_I, [_P, _I, _P, _P, _L, _P, _P]),

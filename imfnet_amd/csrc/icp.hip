@@ -44,6 +44,21 @@
 // 2 (max_iteration + 1) launches and never waits inside the loop; once the device's done flag is up, the remaining
 // launches return at once.  No fp64 atomics anywhere: two runs are bit-identical.  No workgroup ever waits for
 // another one.
+//
+// What the tests pin (tests/registration_cases.py, tests/test_gpu_registration_exact.py):
+//   - the bound: ICP keeps d^2 < r^2 (a target at exactly r is no correspondence), count and pairs keep d^2 <= r^2;
+//   - ties: equal d^2 go to the lowest ORIGINAL target index, whichever cell is probed first and whatever order the
+//     scatter gave a cell; of exact duplicates the first occurrence wins;
+//   - cells: cell = floor(x * inv_cell) with inv_cell = (1 - 1e-9) / r, so x = k r lies in cell k - 1 for k > 0 and in
+//     cell k for k <= 0;
+//   - the key range: a TARGET must lie in cells [-(2^17 - 1), 2^17 - 2] on every axis; one in the next cell, or a NaN,
+//     raises the error flag (the wrappers raise ImfError).  A QUERY searches from cells [-2^17, 2^17 - 1]; beyond them,
+//     or NaN, it finds nothing.  A query in an outermost cell probes a neighbour whose 18-bit key wraps to the other end
+//     of the range: that cell is one no target may occupy, so nothing aliases;
+//   - the update of a rank-deficient correspondence set is a proper rotation by the rank rule of registration.h: one
+//     correspondence, or all on one target point, give R = I and the pure translation md - ms.  The zero must be exact
+//     for that: the covariance is formed in one pass, sum s d^T - (sum s) md^T, and on generic coordinates a set whose
+//     exact covariance is 0 leaves rounding noise there, whose fit is some proper rotation about the centroids.
 #include "common.h"
 #include "registration.h"
 

@@ -13,6 +13,8 @@
 // max_iteration hypotheses are drawn.  Open3D seeds its generator from std::random_device, so the
 // reference's draw sequence cannot be reproduced; this implementation and its oracle restatement share
 // a counter-based generator (splitmix64 of seed, iteration, pick) and agree hypothesis by hypothesis.
+// Samples are drawn with replacement: a repeated pick passes the edge-length checker (0 against 0) and its fit is rank
+// deficient; registration.h's rank rule makes that fit a proper rotation all the same (rank 0: a pure translation).
 //
 // On the GPU the 50 000 hypotheses are independent: one thread fits and checks each (fp64, 3x3
 // one-sided Jacobi SVD), one wavefront scores each surviving hypothesis over all correspondences, one
@@ -163,6 +165,30 @@ __global__ __launch_bounds__(1024) void k_ransac_select(const int32_t *__restric
 using namespace imf;
 
 extern "C" {
+
+// host only: the fit of registration.h on CPU arrays, any n >= 1 (the sums of rigid_fit, then the same rigid_from_cov)
+int imf_host_rigid_fit(const double *src, const double *dst, int n, double *T12) {
+  IMF_REQUIRE(src && dst && T12, "imf_host_rigid_fit: null pointer");
+  IMF_REQUIRE(n >= 1, "imf_host_rigid_fit: n=%d", n);
+  V3 ms{0, 0, 0}, md{0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const V3 s = load3(src, i), d = load3(dst, i);
+    ms.x += s.x; ms.y += s.y; ms.z += s.z;
+    md.x += d.x; md.y += d.y; md.z += d.z;
+  }
+  const double inv = 1.0 / n;
+  ms = {ms.x * inv, ms.y * inv, ms.z * inv};
+  md = {md.x * inv, md.y * inv, md.z * inv};
+  double B[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  for (int i = 0; i < n; ++i) {
+    const V3 a = sub(load3(src, i), ms), b = sub(load3(dst, i), md);
+    const double av[3] = {a.x, a.y, a.z}, bv[3] = {b.x, b.y, b.z};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) B[r][c] += av[r] * bv[c];
+  }
+  rigid_from_cov(ms, md, B, T12);
+  return IMF_OK;
+}
 
 size_t imf_ransac_workspace_bytes(int max_iter) {
   if (max_iter <= 0) return 0;

@@ -885,6 +885,11 @@ int imf_ransac_registration(const double *src, int64_t n_src, const double *dst,
                             const int32_t *corres, int ransac_n, double max_corr_dist, double edge_similarity,
                             int max_iter, uint64_t seed, double *out_T, int32_t *out_meta, double *out_stats,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* [host pointers, no GPU] The rigid fit dst ~ R src + t that RANSAC's hypotheses and ICP's iterations share
+ * (csrc/registration.h), on n >= 1 pairs src, dst [n,3]: T12 receives the row-major 3x4 [R | t].  R is a proper
+ * rotation for every input: the SVD answer at rank 3 and 2; at rank 1 the least-angle rotation between the two
+ * directions (a half turn about a fixed perpendicular axis when they are opposite); at rank 0 the identity. */
+int imf_host_rigid_fit(const double *src, const double *dst, int n, double *T12);
 
 /* ---- Point-to-point ICP and the radius-count overlap test (the KITTI evaluation, imfnet_amd/evaluate_kitti.py) ----
  * imf_icp_point_to_point replaces Open3D 0.12 registration_icp(src, dst, max_corr_dist, init,

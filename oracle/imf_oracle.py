@@ -581,12 +581,62 @@ def _splitmix64(x):
         return x ^ (x >> np.uint64(31))
 
 
-def rigid_fit(src, dst):
-    """TransformationEstimationPointToPoint(False) = Eigen::umeyama without scale, batched:
-    src, dst [..., n, 3] -> [..., 4, 4] with dst ~ R src + t."""
-    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
-    ms, md = src.mean(-2, keepdims=True), dst.mean(-2, keepdims=True)
-    H = np.swapaxes(src - ms, -1, -2) @ (dst - md)
+def jacobi_column_norms(H):
+    """The column norms of B = H V after the one-sided Jacobi sweeps of csrc/registration.h (batched, [..., 3, 3] ->
+    [..., 3]): what the rank rule of `rigid_rotation` is stated on.  LAPACK's small singular values of a rank-deficient
+    matrix are rounding noise of the size of the threshold itself; the sweeps drive a dependent column to the square
+    of that, so the decision is the same on both sides of a comparison."""
+    B = np.array(H, np.float64)
+    shape = B.shape[:-2]
+    B = B.reshape(-1, 3, 3).copy()
+    live = np.ones(len(B), bool)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for _ in range(12):
+            off = np.zeros(len(B))
+            for p, q in ((0, 1), (0, 2), (1, 2)):
+                bp, bq = B[:, :, p].copy(), B[:, :, q].copy()
+                al, be, ga = (bp * bp).sum(1), (bq * bq).sum(1), (bp * bq).sum(1)
+                off = np.where(live, np.maximum(off, np.abs(ga) / (np.sqrt(al * be) + 1e-300)), off)
+                rot = live & (np.abs(ga) > 1e-300)
+                zeta = (be - al) / (2.0 * np.where(rot, ga, 1.0))
+                t = np.where(zeta >= 0, 1.0, -1.0) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+                c = 1.0 / np.sqrt(1.0 + t * t)
+                sn = c * t
+                c, sn = np.where(rot, c, 1.0)[:, None], np.where(rot, sn, 0.0)[:, None]
+                B[:, :, p] = c * bp - sn * bq
+                B[:, :, q] = sn * bp + c * bq
+            live &= ~(off < 1e-15)
+            if not live.any():
+                break
+    return np.sqrt((B * B).sum(1)).reshape(shape + (3,))
+
+
+def rotation_between(u, v):
+    """The least-angle rotation that takes the unit vector u to v (batched [..., 3]), as two half turns, about u and about
+    the bisector h = u + v.  Opposite vectors (|u + v|^2 <= 2^-40): the half turn about the coordinate axis e_j of the
+    smallest |u_j| (lowest j on ties) made perpendicular to u."""
+    u, v = np.asarray(u, np.float64), np.asarray(v, np.float64)
+    eye = np.broadcast_to(np.eye(3), u.shape[:-1] + (3, 3))
+    h = u + v
+    uu, hh = (u * u).sum(-1)[..., None, None], (h * h).sum(-1)[..., None, None]
+    hu = (h * u).sum(-1)[..., None, None]
+    outer = lambda a, b: a[..., :, None] * b[..., None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        R = eye - 2.0 * outer(u, u) / uu - 2.0 * outer(h, h) / hh + 4.0 * hu * outer(h, u) / (hh * uu)
+    j = np.argmin(np.abs(u), -1)                                          # first minimum: lowest j on ties
+    ej = np.eye(3)[j]
+    ax = ej - np.take_along_axis(u, j[..., None], -1) / uu[..., 0] * u
+    half = 2.0 * outer(ax, ax) / (ax * ax).sum(-1)[..., None, None] - eye
+    return np.where(hh > 2.0 ** -40, R, half)
+
+
+def rigid_rotation(H):
+    """R [..., 3, 3] of the fit from the cross-covariance H = sum (s - ms)(d - md)^T, a proper rotation for every H.
+    Rank 3 and 2: Eigen::umeyama's V diag(1, 1, det) U^T.  The rank rule shared with csrc/registration.h: a column of
+    H V after the Jacobi sweeps is zero when its norm is <= 2^-52 of the largest; rank 1: the least-angle rotation from
+    the source direction to the target direction (`rotation_between`; Eigen's answer there is an artefact of its sweep
+    order, every rotation about the line has the same residual); rank 0: the identity (Eigen's and LAPACK's answer)."""
+    H = np.asarray(H, np.float64)
     U, _, Vt = np.linalg.svd(H)
     V = np.swapaxes(Vt, -1, -2)
     d = np.sign(np.linalg.det(V @ np.swapaxes(U, -1, -2)))
@@ -594,6 +644,21 @@ def rigid_fit(src, dst):
     D[..., 0, 0] = D[..., 1, 1] = 1.0
     D[..., 2, 2] = d
     R = V @ D @ np.swapaxes(U, -1, -2)
+    sg = jacobi_column_norms(H)
+    rank = (sg > sg.max(-1, keepdims=True) * 2.0 ** -52).sum(-1)[..., None, None]
+    if (rank < 2).any():
+        R = np.where(rank == 1, rotation_between(U[..., :, 0], V[..., :, 0]), R)
+        R = np.where(rank == 0, np.eye(3), R)
+    return R
+
+
+def rigid_fit(src, dst):
+    """TransformationEstimationPointToPoint(False) = Eigen::umeyama without scale, batched:
+    src, dst [..., n, 3] -> [..., 4, 4] with dst ~ R src + t.  Rank-deficient sets: the rank rule of `rigid_rotation`."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    ms, md = src.mean(-2, keepdims=True), dst.mean(-2, keepdims=True)
+    H = np.swapaxes(src - ms, -1, -2) @ (dst - md)
+    R = rigid_rotation(H)
     T = np.zeros(H.shape[:-2] + (4, 4))
     T[..., :3, :3] = R
     T[..., :3, 3] = md[..., 0, :] - (R @ ms[..., 0, :, None])[..., 0]

@@ -37,21 +37,31 @@ def poses_text(positions):
     return "".join(" ".join(f"{v:.9e}" for v in P[:3].reshape(-1)) + "\n" for P in positions)
 
 
-def icp_restated(src, dst, r, init=None, max_iteration=200):
+def icp_restated(src, dst, r, init=None, max_iteration=200, nearest=None, rotation=None):
     """Open3D 0.12 RegistrationICP, point-to-point, relative fitness / rmse 1e-6, on cKDTree (distance_upper_bound=r:
-    strict).  Returns (T, fitness, rmse, iterations, n_corr)."""
-    from scipy.spatial import cKDTree
+    strict).  Returns (T, fitness, rmse, iterations, n_corr).  The update's rotation follows the rank rule of
+    imf_oracle.rigid_rotation (full rank: the SVD answer, unchanged).  `nearest(p) -> (ok bool [n], j int [n], d2 [n])`
+    replaces the cKDTree search (registration_cases.nearest_brute: ties to the lowest target index); `rotation(H) -> R`
+    replaces the rotation of the update (the tests pass the plain SVD formula to show that full rank is unchanged)."""
+    import imf_oracle as O
+    rotation = rotation or O.rigid_rotation
     src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
-    tree = cKDTree(dst)
+    if nearest is None:
+        from scipy.spatial import cKDTree
+        tree = cKDTree(dst)
+
+        def nearest(p):
+            d, j = tree.query(p, k=1, distance_upper_bound=r)
+            ok = np.isfinite(d)
+            return ok, np.where(ok, j, 0), np.where(ok, d, 0.0) ** 2
     T = np.eye(4) if init is None else np.array(init, np.float64)
     pcd = src @ T[:3, :3].T + T[:3, 3]
 
     def corr(p):
-        d, j = tree.query(p, k=1, distance_upper_bound=r)
-        ok = np.isfinite(d)
+        ok, j, d2 = nearest(p)
         n = int(ok.sum())
         fit = n / len(p) if n else 0.0
-        rmse = float(np.sqrt((d[ok] ** 2).sum() / n)) if n else 0.0
+        rmse = float(np.sqrt(d2[ok].sum() / n)) if n else 0.0
         return np.flatnonzero(ok), j[ok], fit, rmse
 
     i_s, i_d, fit, rmse = corr(pcd)
@@ -61,8 +71,7 @@ def icp_restated(src, dst, r, init=None, max_iteration=200):
             S, D = pcd[i_s], dst[i_d]
             ms, md = S.mean(0), D.mean(0)
             H = (S - ms).T @ (D - md)
-            U, _, Vt = np.linalg.svd(H)
-            R = Vt.T @ np.diag([1, 1, np.sign(np.linalg.det(Vt.T @ U.T))]) @ U.T
+            R = rotation(H)
             upd = np.eye(4)
             upd[:3, :3] = R
             upd[:3, 3] = md - R @ ms
