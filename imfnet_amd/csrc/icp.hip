@@ -59,8 +59,22 @@
 //     correspondence, or all on one target point, give R = I and the pure translation md - ms.  The zero must be exact
 //     for that: the covariance is formed in one pass, sum s d^T - (sum s) md^T, and on generic coordinates a set whose
 //     exact covariance is 0 leaves rounding noise there, whose fit is some proper rotation about the centroids.
+//
+// Point-to-plane ICP (imf_icp_point_to_plane).  Open3D registration_icp with TransformationEstimationPointToPlane(),
+// restated ([RECALLED]; no Open3D to check against).  The loop, the correspondence rule (strict d^2 < r^2, ties -> lowest
+// original index), fitness, rmse (over POINT distances, not plane residuals), T = update . T, the stop rule and the launch
+// pattern are the point-to-point ones above; only the update differs:
+//   r_i = (p_i - q_i) . n_i,  J_i = [p_i x n_i, n_i]  (rotation first),  solve (sum J^T J) x = -(sum J^T r),
+//   update = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5]
+// with p the current source point, q its target and n the target's normal.  k_icp_corr<true> writes per block the fp64
+// partial sums count, sum d^2, the 21 upper entries of J^T J (row-major) and the 6 of J^T r; k_icp_fit<true> adds the block
+// rows in the fixed order of the point-to-point fit and solves the 6x6 system by LDL^T without pivoting.
+// The singular rule: when a pivot d_k <= 1e-12 * (the largest diagonal entry of sum J^T J), or is NaN, the update is the
+// identity (as is the update of an empty correspondence set).  A single-plane target (rank 3) and fewer than 6 independent
+// rows end there: the next stage then repeats the statistics and the stop rule ends the loop at iteration 1.
 #include "common.h"
 #include "registration.h"
+#include "point_grid.h"
 
 namespace imf {
 namespace {
@@ -69,17 +83,8 @@ constexpr int kIcpThreads = 256;
 constexpr int kIcpSums = 17;           // count, sum d^2, sum s[3], sum d[3], sum s d^T [9]
 constexpr int kIcpRow = 18;            // doubles per block row (padded)
 constexpr int kFitThreads = 256;
-
-// cell-CSR grid over the target
-struct Grid {
-  imf_slot *tab;                        // key -> (val = first sorted row, pad = count) after the scan
-  uint32_t capmask;
-  int32_t *cnt;                         // [cap] points per slot, then the scatter cursor
-  int32_t *cell_of;                     // [n_dst] slot of every target point
-  double *xyz;                          // [n_dst, 3] target sorted by cell
-  int32_t *idx;                         // [n_dst] original index of every sorted row
-  double inv_cell;
-};
+constexpr int kPlaneSums = 29;         // point-to-plane: count, sum d^2, upper J^T J [21], J^T r [6]
+constexpr int kPlaneRow = 30;          // doubles per block row (padded)
 
 struct IcpInit {
   double T[16];                         // row-major 4x4, by value (a host matrix)
@@ -91,75 +96,6 @@ struct IcpState {
   double fitness, rmse;
   int32_t n_corr, iters, done, pad;
 };
-
-__device__ __forceinline__ bool cell_of_point(V3 p, double inv_cell, int lim, int &x, int &y, int &z) {
-  const double fx = floor(p.x * inv_cell), fy = floor(p.y * inv_cell), fz = floor(p.z * inv_cell);
-  if (!(fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim)) return false;   // NaN too
-  x = (int)fx; y = (int)fy; z = (int)fz;
-  return true;
-}
-
-__global__ __launch_bounds__(256) void k_grid_init(imf_slot *tab, int32_t *cnt, int64_t cap, int32_t *err) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *err = 0;
-  if (i < cap) {
-    reinterpret_cast<uint4 *>(tab)[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-    cnt[i] = 0;
-  }
-}
-
-// target cells are kept one cell inside the key range, so that a query cell's 26 neighbours never wrap
-__global__ __launch_bounds__(256) void k_grid_insert(const double *__restrict__ dst, int64_t n, Grid g, int32_t *err) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  int x, y, z;
-  if (!cell_of_point(load3(dst, j), g.inv_cell, kCoordLim - 1, x, y, z)) {
-    atomicOr(err, 1);
-    g.cell_of[j] = -1;
-    return;
-  }
-  const uint32_t s = hash_insert(g.tab, g.capmask, pack_key(0, x, y, z), 0);
-  g.cell_of[j] = (int32_t)s;
-  atomicAdd(&g.cnt[s], 1);
-}
-
-// one workgroup: exclusive scan of the per-slot counts in slot order -> tab[s].val = first row, tab[s].pad = count,
-// cnt[s] = scatter cursor
-__global__ __launch_bounds__(1024) void k_grid_scan(Grid g, int64_t cap) {
-  __shared__ int32_t part[1024];
-  const int t = threadIdx.x;
-  const int64_t per = (cap + 1023) / 1024, b = t * per, e = min(cap, b + per);
-  int32_t sum = 0;
-  for (int64_t s = b; s < e; ++s) sum += g.cnt[s];
-  part[t] = sum;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {                 // Hillis-Steele inclusive scan
-    const int32_t v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int32_t run = part[t] - sum;
-  for (int64_t s = b; s < e; ++s) {
-    const int32_t c = g.cnt[s];
-    g.tab[s].val = run;
-    g.tab[s].pad = c;
-    g.cnt[s] = run;
-    run += c;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_grid_scatter(const double *__restrict__ dst, int64_t n, Grid g) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const int32_t s = g.cell_of[j];
-  if (s < 0) return;
-  const int32_t r = atomicAdd(&g.cnt[s], 1);
-  g.xyz[3 * (int64_t)r + 0] = dst[3 * j + 0];
-  g.xyz[3 * (int64_t)r + 1] = dst[3 * j + 1];
-  g.xyz[3 * (int64_t)r + 2] = dst[3 * j + 2];
-  g.idx[r] = (int32_t)j;
-}
 
 // nearest target (d^2 < r2, ties -> lowest original index) of p; returns its sorted row or -1
 __device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, double &best_d2) {
@@ -211,16 +147,19 @@ __global__ __launch_bounds__(256) void k_icp_start(const double *__restrict__ sr
   cur[3 * i + 0] = p.x; cur[3 * i + 1] = p.y; cur[3 * i + 2] = p.z;
 }
 
-// stage k: k = 0 on the initial points, k = i + 1 after the update of iteration i
-__global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, double *__restrict__ cur, int64_t n, double r2,
-                                                          int stage, const IcpState *__restrict__ st,
-                                                          double *__restrict__ partial) {
+// stage k: k = 0 on the initial points, k = i + 1 after the update of iteration i.  kPlane: the point-to-plane sums, with
+// normals [n_dst, 3] in the target's ORIGINAL order (unused otherwise)
+template <bool kPlane>
+__global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, const double *__restrict__ normals,
+                                                          double *__restrict__ cur, int64_t n, double r2, int stage,
+                                                          const IcpState *__restrict__ st, double *__restrict__ partial) {
   if (st->done) return;
+  constexpr int kSums = kPlane ? kPlaneSums : kIcpSums, kRow = kPlane ? kPlaneRow : kIcpRow;
   __shared__ double lds4[4];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double v[kIcpSums];
+  double v[kSums];
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
+  for (int k = 0; k < kSums; ++k) v[k] = 0.0;
   if (i < n) {
     V3 p = load3(cur, i);
     if (stage > 0) {
@@ -231,33 +170,79 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, double *__rest
     const int r = grid_nearest(g, p, r2, d2);
     if (r >= 0) {
       const V3 q = load3(g.xyz, r);
-      const double sv[3] = {p.x, p.y, p.z}, dv[3] = {q.x, q.y, q.z};
       v[0] = 1.0;
       v[1] = d2;
-      for (int a = 0; a < 3; ++a) {
-        v[2 + a] = sv[a];
-        v[5 + a] = dv[a];
-        for (int b = 0; b < 3; ++b) v[8 + 3 * a + b] = sv[a] * dv[b];
+      if constexpr (kPlane) {
+        const V3 nq = load3(normals, g.idx[r]);
+        const V3 c = cross(p, nq);
+        const double res = dot(sub(p, q), nq);
+        const double J[6] = {c.x, c.y, c.z, nq.x, nq.y, nq.z};
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int b = a; b < 6; ++b) v[k++] = J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * res;
+      } else {
+        const double sv[3] = {p.x, p.y, p.z}, dv[3] = {q.x, q.y, q.z};
+        for (int a = 0; a < 3; ++a) {
+          v[2 + a] = sv[a];
+          v[5 + a] = dv[a];
+          for (int b = 0; b < 3; ++b) v[8 + 3 * a + b] = sv[a] * dv[b];
+        }
       }
     }
   }
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) {
+  for (int k = 0; k < kSums; ++k) {
     const double s = block_sum(v[k], lds4);
-    if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * kIcpRow + k] = s;
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * kRow + k] = s;
   }
 }
 
+// x of A x = -b for the symmetric 6x6 A by LDL^T without pivoting; false under the singular rule of the file header
+__device__ bool solve_plane_system(const double A[6][6], const double b[6], double x[6]) {
+  double L[6][6], D[6], big = 0.0;
+  for (int k = 0; k < 6; ++k) big = fmax(big, A[k][k]);
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
+    if (!(d > 1e-12 * big)) return false;               // zero, negative, tiny or NaN
+    D[j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k] * D[k];
+      L[i][j] = s / d;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {                          // L y = -b
+    double s = -b[i];
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s;
+  }
+  for (int i = 5; i >= 0; --i) {                         // L^T x = D^-1 y
+    double s = y[i] / D[i];
+    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * x[k];
+    x[i] = s;
+  }
+  return true;
+}
+
+// one workgroup per stage; kPlane selects the sums' layout and the update (point-to-point: Umeyama, point-to-plane: LDL^T)
+template <bool kPlane>
 __global__ __launch_bounds__(kFitThreads) void k_icp_fit(const double *__restrict__ partial, int n_blocks, int64_t n_src,
                                                          int stage, int max_iteration, IcpState *st, double *out_T,
                                                          double *out_stats, int32_t *out_meta) {
   if (st->done) return;
   __shared__ double lds[kFitThreads];
-  __shared__ double sums[kIcpSums];
+  constexpr int kSums = kPlane ? kPlaneSums : kIcpSums, kRow = kPlane ? kPlaneRow : kIcpRow;
+  __shared__ double sums[kSums];
   const int t = threadIdx.x;
-  for (int k = 0; k < kIcpSums; ++k) {
+  for (int k = 0; k < kSums; ++k) {
     double a = 0.0;
-    for (int b = t; b < n_blocks; b += kFitThreads) a += partial[(int64_t)b * kIcpRow + k];   // ascending per thread
+    for (int b = t; b < n_blocks; b += kFitThreads) a += partial[(int64_t)b * kRow + k];   // ascending per thread
     lds[t] = a;
     __syncthreads();
     for (int o = kFitThreads / 2; o > 0; o >>= 1) {     // fixed tree
@@ -283,7 +268,19 @@ __global__ __launch_bounds__(kFitThreads) void k_icp_fit(const double *__restric
   st->n_corr = n_corr;
   if (!done) {
     double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    if (n_corr > 0) {
+    if constexpr (kPlane) {
+      double A[6][6], b[6], x[6];
+      int k = 2;
+      for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c) A[a][c] = A[c][a] = sums[k++];
+      for (int a = 0; a < 6; ++a) b[a] = sums[23 + a];
+      if (n_corr > 0 && solve_plane_system(A, b, x)) {
+        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+        U[0] = cg * cb; U[1] = cg * sb * sa - sg * ca; U[2] = cg * sb * ca + sg * sa;  U[3] = x[3];   // Rz Ry Rx
+        U[4] = sg * cb; U[5] = sg * sb * sa + cg * ca; U[6] = sg * sb * ca - cg * sa;  U[7] = x[4];
+        U[8] = -sb;     U[9] = cb * sa;                U[10] = cb * ca;                U[11] = x[5];
+      }
+    } else if (n_corr > 0) {
       const double inv = 1.0 / cnt;
       const V3 ms{sums[2] * inv, sums[3] * inv, sums[4] * inv}, md{sums[5] * inv, sums[6] * inv, sums[7] * inv};
       const double sv[3] = {sums[2], sums[3], sums[4]}, mdv[3] = {md.x, md.y, md.z};
@@ -404,40 +401,47 @@ __global__ __launch_bounds__(256) void k_pairs_emit(Grid g, const double *__rest
   }
 }
 
-// workspace layout of the grid (all offsets 256-byte aligned)
-struct GridLayout {
-  int64_t cap;
-  size_t tab, cnt, cell_of, xyz, idx, err, total;
-};
-GridLayout grid_layout(int64_t n_dst) {
-  GridLayout L;
-  L.cap = imf_hash_capacity(n_dst);
-  size_t p = 0;
-  L.tab = p;     p += align256((size_t)L.cap * sizeof(imf_slot));
-  L.cnt = p;     p += align256((size_t)L.cap * 4);
-  L.cell_of = p; p += align256((size_t)n_dst * 4);
-  L.xyz = p;     p += align256((size_t)n_dst * 24);
-  L.idx = p;     p += align256((size_t)n_dst * 4);
-  L.err = p;     p += 256;
-  L.total = p;
-  return L;
+size_t icp_workspace_bytes(int64_t n_src, int64_t n_dst, int row) {
+  if (n_src <= 0 || n_dst <= 0) return 0;
+  const size_t nb = (size_t)div_up(n_src, kIcpThreads);
+  return grid_layout(n_dst).total + align256((size_t)n_src * 24) + align256(nb * row * 8) + align256(sizeof(IcpState));
 }
 
-int build_grid(const double *dst, int64_t n_dst, double cell, char *ws, Grid &g, int32_t *&err, hipStream_t st) {
-  const GridLayout L = grid_layout(n_dst);
-  g.tab = (imf_slot *)(ws + L.tab);
-  g.capmask = (uint32_t)(L.cap - 1);
-  g.cnt = (int32_t *)(ws + L.cnt);
-  g.cell_of = (int32_t *)(ws + L.cell_of);
-  g.xyz = (double *)(ws + L.xyz);
-  g.idx = (int32_t *)(ws + L.idx);
-  g.inv_cell = (1.0 - 1e-9) / cell;   // a hair over r: rounding in p * inv_cell can never put a point within r two cells away
-  err = (int32_t *)(ws + L.err);
-  k_grid_init<<<(unsigned)div_up(L.cap, 256), 256, 0, st>>>(g.tab, g.cnt, L.cap, err);
-  k_grid_insert<<<(unsigned)div_up(n_dst, 256), 256, 0, st>>>(dst, n_dst, g, err);
-  k_grid_scan<<<1, 1024, 0, st>>>(g, L.cap);
-  k_grid_scatter<<<(unsigned)div_up(n_dst, 256), 256, 0, st>>>(dst, n_dst, g);
-  IMF_CHECK_LAUNCH("imf icp grid build");
+// both ICP entry points: the argument checks, the grid, 2 (max_iteration + 1) launches; normals: point-to-plane only
+template <bool kPlane>
+int icp_run(const char *name, const double *src, int64_t n_src, const double *dst, const double *normals, int64_t n_dst,
+            double max_corr_dist, const double *init_host, int max_iteration, double *out_T, double *out_stats,
+            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
+  constexpr int kRow = kPlane ? kPlaneRow : kIcpRow;
+  IMF_REQUIRE(src && dst && (normals || !kPlane) && out_T && out_stats && out_meta && workspace, "%s: null pointer", name);
+  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst < (1ll << 30), "%s: n_src=%lld n_dst=%lld", name,
+              (long long)n_src, (long long)n_dst);
+  IMF_REQUIRE(max_corr_dist > 0.0 && max_corr_dist < 1e6, "%s: max_corr_dist=%g", name, max_corr_dist);
+  IMF_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, "%s: max_iteration=%d", name, max_iteration);
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", name);
+  IMF_REQUIRE(workspace_bytes >= icp_workspace_bytes(n_src, n_dst, kRow), "%s: workspace %zu < %zu", name, workspace_bytes,
+              icp_workspace_bytes(n_src, n_dst, kRow));
+  hipStream_t st = (hipStream_t)stream;
+  char *ws = (char *)workspace;
+  Grid g;
+  int32_t *err;
+  int rc = build_grid(dst, n_dst, max_corr_dist, ws, g, err, st);
+  if (rc) return rc;
+  size_t p = grid_layout(n_dst).total;
+  const int nb = (int)div_up(n_src, kIcpThreads);
+  double *cur = (double *)(ws + p);     p += align256((size_t)n_src * 24);
+  double *partial = (double *)(ws + p); p += align256((size_t)nb * kRow * 8);
+  IcpState *state = (IcpState *)(ws + p);
+  IcpInit init;
+  for (int k = 0; k < 16; ++k) init.T[k] = init_host ? init_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
+  k_icp_start<<<(unsigned)nb, 256, 0, st>>>(src, n_src, init, cur, state);
+  const double r2 = max_corr_dist * max_corr_dist;
+  for (int stage = 0; stage <= max_iteration; ++stage) {
+    k_icp_corr<kPlane><<<(unsigned)nb, kIcpThreads, 0, st>>>(g, normals, cur, n_src, r2, stage, state, partial);
+    k_icp_fit<kPlane><<<1, kFitThreads, 0, st>>>(partial, nb, n_src, stage, max_iteration, state, out_T, out_stats, out_meta);
+  }
+  IMF_CHECK_LAUNCH(name);
+  IMF_CHECK_HIP(hipMemcpyAsync(out_meta + 2, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   return IMF_OK;
 }
 
@@ -448,45 +452,22 @@ using namespace imf;
 
 extern "C" {
 
-size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst) {
-  if (n_src <= 0 || n_dst <= 0) return 0;
-  const size_t nb = (size_t)div_up(n_src, kIcpThreads);
-  return grid_layout(n_dst).total + align256((size_t)n_src * 24) + align256(nb * kIcpRow * 8) + align256(sizeof(IcpState));
-}
+size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_workspace_bytes(n_src, n_dst, kIcpRow); }
 
 int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
                            const double *init_host, int max_iteration, double *out_T, double *out_stats,
                            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
-  IMF_REQUIRE(src && dst && out_T && out_stats && out_meta && workspace, "imf_icp_point_to_point: null pointer");
-  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst < (1ll << 30),
-              "imf_icp_point_to_point: n_src=%lld n_dst=%lld", (long long)n_src, (long long)n_dst);
-  IMF_REQUIRE(max_corr_dist > 0.0 && max_corr_dist < 1e6, "imf_icp_point_to_point: max_corr_dist=%g", max_corr_dist);
-  IMF_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, "imf_icp_point_to_point: max_iteration=%d", max_iteration);
-  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_icp_point_to_point: workspace must be 256-byte aligned");
-  IMF_REQUIRE(workspace_bytes >= imf_icp_workspace_bytes(n_src, n_dst), "imf_icp_point_to_point: workspace %zu < %zu",
-              workspace_bytes, imf_icp_workspace_bytes(n_src, n_dst));
-  hipStream_t st = (hipStream_t)stream;
-  char *ws = (char *)workspace;
-  Grid g;
-  int32_t *err;
-  int rc = build_grid(dst, n_dst, max_corr_dist, ws, g, err, st);
-  if (rc) return rc;
-  size_t p = grid_layout(n_dst).total;
-  const int nb = (int)div_up(n_src, kIcpThreads);
-  double *cur = (double *)(ws + p);     p += align256((size_t)n_src * 24);
-  double *partial = (double *)(ws + p); p += align256((size_t)nb * kIcpRow * 8);
-  IcpState *state = (IcpState *)(ws + p);
-  IcpInit init;
-  for (int k = 0; k < 16; ++k) init.T[k] = init_host ? init_host[k] : (k % 5 == 0 ? 1.0 : 0.0);
-  k_icp_start<<<(unsigned)nb, 256, 0, st>>>(src, n_src, init, cur, state);
-  const double r2 = max_corr_dist * max_corr_dist;
-  for (int stage = 0; stage <= max_iteration; ++stage) {
-    k_icp_corr<<<(unsigned)nb, kIcpThreads, 0, st>>>(g, cur, n_src, r2, stage, state, partial);
-    k_icp_fit<<<1, kFitThreads, 0, st>>>(partial, nb, n_src, stage, max_iteration, state, out_T, out_stats, out_meta);
-  }
-  IMF_CHECK_LAUNCH("imf_icp_point_to_point");
-  IMF_CHECK_HIP(hipMemcpyAsync(out_meta + 2, err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  return IMF_OK;
+  return icp_run<false>("imf_icp_point_to_point", src, n_src, dst, nullptr, n_dst, max_corr_dist, init_host, max_iteration,
+                        out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
+}
+
+size_t imf_icp_plane_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_workspace_bytes(n_src, n_dst, kPlaneRow); }
+
+int imf_icp_point_to_plane(const double *src, int64_t n_src, const double *dst, const double *dst_normals, int64_t n_dst,
+                           double max_corr_dist, const double *init_host, int max_iteration, double *out_T,
+                           double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
+  return icp_run<true>("imf_icp_point_to_plane", src, n_src, dst, dst_normals, n_dst, max_corr_dist, init_host,
+                       max_iteration, out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
 }
 
 size_t imf_radius_count_workspace_bytes(int64_t n_dst) {

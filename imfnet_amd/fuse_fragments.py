@@ -12,8 +12,11 @@ first frame has no pose writes nothing; voxel length --tsdf_cubic_size / 512 and
 The project's own: --voxel_length and --lattice_offset (0.5 = upstream's voxel centres; 0 with --voxel_length 0.006
 gives the lattice of the published 3DMatch fragments); --write_image copies the first integrated frame's
 colour file to cloud_bin_K_0.jpg, the name generate_desc and the trainer look for (upstream writes no image; which frame
-its data set used is not recorded).  The PLY holds float x, y, z only: no colours, no normals.  --threads sizes the
-decode pool (upstream: joblib workers); the next fragment is decoded while the GPU works on the current one.
+its data set used is not recorded).  The PLY holds float x, y, z only, no colours; --normals adds float nx, ny, nz as
+upstream's fragments carry them (estimate_normals after the extract: knn 30, within 5 voxel lengths, facing the
+fragment's first camera, the origin; upstream signs them by the TSDF gradient and sums the covariance as cumulants).
+--threads sizes the decode pool (upstream: joblib workers); the next fragment is decoded while the GPU works on the
+current one.
 """
 import argparse
 import concurrent.futures as cf
@@ -126,8 +129,30 @@ def write_ply(path, xyz):
     _lib.check(rc, f"imf_ply_write_points({path})")
 
 
-def write_fragment(cfg, out_folder, frag_id, frag, xyz):
-    write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz)
+def write_ply_normals(path, xyz, normals):
+    """write_ply's layout (binary little-endian, float32, the same x, y, z bytes) with `float nx, ny, nz` after them; the
+    file appears under its name only when it is complete."""
+    body = np.concatenate([np.asarray(xyz, np.float64), np.asarray(normals, np.float64)], 1).astype("<f4")
+    head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(body)}\nproperty float x\nproperty float y\n"
+            "property float z\nproperty float nx\nproperty float ny\nproperty float nz\nend_header\n")
+    with open(path + ".tmp", "wb") as fh:
+        fh.write(head.encode("ascii"))
+        fh.write(body.tobytes())
+    os.replace(path + ".tmp", path)
+
+
+def fragment_normals(cfg, xyz):
+    from .matching import estimate_normals
+    if len(xyz) == 0:
+        return np.zeros((0, 3))
+    return estimate_normals(xyz, knn=30, max_radius=5.0 * cfg.voxel_length, viewpoint=np.zeros(3), device=cfg.device)[0]
+
+
+def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None):
+    if normals is None:
+        write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz)
+    else:
+        write_ply_normals(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz, normals)
     np.save(os.path.join(out_folder, f"cloud_bin_{frag_id}.pose.npy"), frag["base"])
     with open(os.path.join(out_folder, f"cloud_bin_{frag_id}.frames.pkl"), "wb") as fh:
         pickle.dump({"frames": frag["stems"]}, fh, protocol=pickle.HIGHEST_PROTOCOL)
@@ -142,8 +167,9 @@ def gpu_fuse(cfg, intrinsic, frag):
                          device=cfg.device)
 
 
-def run(cfg, fuse=gpu_fuse, log=print):
-    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` does the volume work.  Returns the fragments written."""
+def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
+    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` does the volume work, `normals(cfg, xyz)` the
+    normals under --normals.  Returns the fragments written."""
     if cfg.voxel_length is None:
         cfg.voxel_length = cfg.tsdf_cubic_size / 512.0
     ensure_dir(cfg.out_root)
@@ -168,7 +194,8 @@ def run(cfg, fuse=gpu_fuse, log=print):
                 log(f"    {scene}/{seq} fragment {k}: no pose for its first frame, nothing written")
                 continue
             xyz = fuse(cfg, intrinsic, frag)
-            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz)
+            nrm = normals(cfg, xyz) if cfg.normals else None
+            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz, nrm)
             written += 1
             log(f"    {scene}/{seq}/cloud_bin_{k}: {len(frag['stems'])} frames, {len(xyz)} points")
     return written
@@ -189,6 +216,8 @@ def parse_args(argv=None):
     ap.add_argument("--lattice_offset", type=float, default=0.5,
                     help="0.5 = voxel centres (upstream); 0 = voxel corners (the published fragments, with --voxel_length 0.006)")
     ap.add_argument("--write_image", action="store_true", help="copy the first integrated frame's colour file to cloud_bin_K_0.jpg")
+    ap.add_argument("--normals", action="store_true",
+                    help="add float nx, ny, nz to the PLY: k-NN PCA normals (knn 30, 5 voxel lengths) facing the first camera")
     ap.add_argument("--device", default="cuda")
     return ap.parse_args(argv)
 

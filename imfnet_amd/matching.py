@@ -157,28 +157,80 @@ def _host_T(T):
     return np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4))
 
 
-def icp_point_to_point(src, dst, max_corr_dist, init=None, max_iteration=200, device="cuda"):
-    """Open3D 0.12 registration_icp(src, dst, max_corr_dist, init, TransformationEstimationPointToPoint(),
-    ICPConvergenceCriteria(max_iteration)) on the device (imf_icp_point_to_point; the loop is restated in
-    csrc/icp.hip).  Returns (T 4x4 numpy source->target, fitness, inlier RMSE, iterations run, correspondences)."""
+def _icp(name, src, dst, normals, max_corr_dist, init, max_iteration, device):
+    """Both ICP entry points: normals None = imf_icp_point_to_point, else imf_icp_point_to_plane."""
     s = _points(src, device, "src")
     d = _points(dst, s.device, "dst")
     L = _lib.lib()
-    nbytes = L.imf_icp_workspace_bytes(s.shape[0], d.shape[0])
+    if normals is None:
+        nbytes = L.imf_icp_workspace_bytes(s.shape[0], d.shape[0])
+    else:
+        nrm = _points(normals, s.device, "dst_normals")
+        if nrm.shape != d.shape:
+            raise ImfError(f"{name}: dst_normals {tuple(nrm.shape)} for dst {tuple(d.shape)}")
+        nbytes = L.imf_icp_plane_workspace_bytes(s.shape[0], d.shape[0])
     ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
     T = torch.empty(16, dtype=torch.float64, device=s.device)
     stats = torch.empty(2, dtype=torch.float64, device=s.device)
     meta = torch.zeros(3, dtype=torch.int32, device=s.device)
     init = _host_T(init)
-    check(L.imf_icp_point_to_point(s.data_ptr(), s.shape[0], d.data_ptr(), d.shape[0], float(max_corr_dist),
-                                   init.ctypes.data_as(C.c_void_p) if init is not None else None, int(max_iteration),
-                                   T.data_ptr(), stats.data_ptr(), meta.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-          "imf_icp_point_to_point")
+    tail = (float(max_corr_dist), init.ctypes.data_as(C.c_void_p) if init is not None else None, int(max_iteration),
+            T.data_ptr(), stats.data_ptr(), meta.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    if normals is None:
+        check(L.imf_icp_point_to_point(s.data_ptr(), s.shape[0], d.data_ptr(), d.shape[0], *tail), "imf_" + name)
+    else:
+        check(L.imf_icp_point_to_plane(s.data_ptr(), s.shape[0], d.data_ptr(), nrm.data_ptr(), d.shape[0], *tail),
+              "imf_" + name)
     iters, n_corr, err = meta.tolist()
     if err:
-        raise ImfError("icp_point_to_point: a target point is NaN or beyond the grid's range")
+        raise ImfError(f"{name}: a target point is NaN or beyond the grid's range")
     fitness, rmse = stats.tolist()
     return T.cpu().numpy().reshape(4, 4), fitness, rmse, iters, n_corr
+
+
+def icp_point_to_point(src, dst, max_corr_dist, init=None, max_iteration=200, device="cuda"):
+    """Open3D 0.12 registration_icp(src, dst, max_corr_dist, init, TransformationEstimationPointToPoint(),
+    ICPConvergenceCriteria(max_iteration)) on the device (imf_icp_point_to_point; the loop is restated in
+    csrc/icp.hip).  Returns (T 4x4 numpy source->target, fitness, inlier RMSE, iterations run, correspondences)."""
+    return _icp("icp_point_to_point", src, dst, None, max_corr_dist, init, max_iteration, device)
+
+
+def icp_point_to_plane(src, dst, dst_normals, max_corr_dist, init=None, max_iteration=30, device="cuda"):
+    """Open3D registration_icp(src, dst, max_corr_dist, init, TransformationEstimationPointToPlane(),
+    ICPConvergenceCriteria(max_iteration)) on the device (imf_icp_point_to_plane; restated in csrc/icp.hip).  dst_normals:
+    [n_dst, 3], row j the normal of dst row j.  Returns what icp_point_to_point returns: (T 4x4 numpy source->target,
+    fitness, inlier RMSE over point distances, iterations run, correspondences)."""
+    if dst_normals is None:
+        raise ImfError("icp_point_to_plane: dst_normals is required")
+    return _icp("icp_point_to_plane", src, dst, dst_normals, max_corr_dist, init, max_iteration, device)
+
+
+def estimate_normals(points, knn=30, max_radius=0.1, viewpoint=None, device="cuda", return_neighbors=False):
+    """o3d.geometry.PointCloud.estimate_normals(KDTreeSearchParamKNN(knn)) on the device, exactly (imf_estimate_normals;
+    the rules are stated in csrc/normals.hip): the PCA normal of every point's knn nearest cloud points within max_radius,
+    itself included.  viewpoint: 3 numbers the normals face, or None = the largest component positive.  Returns (normals
+    float64 numpy [n, 3], counts int32 numpy [n]) and, with return_neighbors=True, the neighbour lists int32 [n, knn]
+    in (d^2, index) order padded with -1."""
+    p = _points(points, device, "points")
+    n = p.shape[0]
+    vp = None
+    if viewpoint is not None:
+        vp = np.ascontiguousarray(np.asarray(viewpoint, dtype=np.float64).reshape(3))
+    L = _lib.lib()
+    nbytes = L.imf_normals_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    normals = torch.empty((n, 3), dtype=torch.float64, device=p.device)
+    counts = torch.empty(n + 1, dtype=torch.int32, device=p.device)          # [n] the error flag
+    nbr = torch.empty((n, int(knn)), dtype=torch.int32, device=p.device) if return_neighbors else None
+    check(L.imf_estimate_normals(p.data_ptr(), n, int(knn), float(max_radius),
+                                 vp.ctypes.data_as(C.c_void_p) if vp is not None else None, normals.data_ptr(),
+                                 counts.data_ptr(), nbr.data_ptr() if return_neighbors else None, counts[n:].data_ptr(),
+                                 ws.data_ptr(), nbytes, _stream()), "imf_estimate_normals")
+    counts = counts.cpu().numpy()
+    if counts[n]:
+        raise ImfError("estimate_normals: a point is NaN or beyond the grid's range")
+    out = (normals.cpu().numpy(), counts[:n].copy())
+    return out + (nbr.cpu().numpy(),) if return_neighbors else out
 
 
 def radius_count(src, dst, T=None, r=0.45, per_point=False, device="cuda"):

@@ -1,0 +1,149 @@
+"""Register one pair of fragments end to end: descriptors, keypoints, RANSAC, ICP refinement.
+
+    python -m imfnet_amd.register --source A.ply --source_image A.png --target B.ply --target_image B.png
+                                  [-m checkpoint.pth] [--refine plane] [--out T.txt]
+
+The stages are the library's own, in the order scripts/evaluation_3dmatch.py and scripts/benchmark_util.py use them:
+`extract_features` on both fragments, the keypoint draw (`num_keypoints` raw points without replacement from
+RandomState(seed), source first) and `select_keypoints`, RANSAC on the nearest-descriptor correspondences (ransac_n = 3,
+1.5 voxel, edge similarity 0.9), then ICP on the voxel representatives at 1.5 voxel: point-to-point, or point-to-plane
+against the target's `estimate_normals(knn=30, max_radius=4 voxel, viewpoint=origin)`.  --skip_global starts the
+refinement from --init (identity when absent); the descriptors are still extracted.  Without -m the network runs on
+the seeded weights of the test oracle: the global stage is then meaningless, the plumbing is the same.
+
+Writes the 4x4 source->target matrix to --out (np.savetxt) and prints one JSON line: fitness, rmse, iterations, n_corr,
+the stage times in seconds and the matrix.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REFINE_CHOICES = ("none", "point", "plane")
+
+
+def load_network(checkpoint, device):
+    """(model on the device, config) of a checkpoint, or of the seeded weights (oracle/imf_oracle.py) when it is None."""
+    from .checkpoint import Config, load_checkpoint
+    from .model import load_model
+    if checkpoint:
+        sd, cfg = load_checkpoint(checkpoint)
+    else:
+        oracle = os.path.join(ROOT, "oracle")
+        if oracle not in sys.path:
+            sys.path.insert(0, oracle)
+        import imf_oracle
+        sd, cfg = imf_oracle.seeded_state_dict(seed=0, with_unused_image_layers=True), Config()
+    model = load_model(cfg.model)(1, cfg.model_n_out, bn_momentum=cfg.bn_momentum, normalize_feature=cfg.normalize_feature,
+                                  conv1_kernel_size=cfg.conv1_kernel_size, D=3, config=cfg)
+    model.load_state_dict(sd, strict=True)
+    return model.eval().to(device), cfg
+
+
+def load_image(path, cfg):
+    from .dataio import image_to_nchw, process_image, read_image
+    img = read_image(path)
+    if img.shape[0] != cfg.image_H or img.shape[1] != cfg.image_W:
+        img = process_image(image=img, aim_H=cfg.image_H, aim_W=cfg.image_W)
+    return image_to_nchw(img)
+
+
+def register_pair(model, cfg, source, source_image, target, target_image, voxel_size=0.025, num_keypoints=5000,
+                  ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda"):
+    """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  Returns
+    dict(T 4x4 numpy source->target, fitness, rmse, iterations, n_corr, times)."""
+    from .extract import extract_features
+    from .matching import (estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search, ransac_registration,
+                           select_keypoints)
+    if refine not in REFINE_CHOICES:
+        raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
+    dev = torch.device(device)
+    times = {}
+
+    def timed(name, t0):
+        torch.cuda.synchronize(dev)
+        times[name] = time.time() - t0
+
+    t0 = time.time()
+    down, feat = [], []
+    with torch.no_grad():
+        for pts, img in ((source, source_image), (target, target_image)):
+            xyz, F = extract_features(model, np.asarray(pts, np.float64), voxel_size=voxel_size, device=dev,
+                                      skip_check=True, image=img)
+            down.append(np.asarray(xyz, np.float64))
+            feat.append(F)
+    timed("features", t0)
+
+    r = 1.5 * voxel_size
+    T = np.eye(4) if init is None else np.asarray(init, np.float64).reshape(4, 4)
+    if not skip_global:
+        t0 = time.time()
+        rng = np.random.RandomState(seed)
+        keys = []
+        for pts, xyz in zip((source, target), down):
+            pts = np.asarray(pts, np.float64)
+            sample = pts[rng.choice(len(pts), min(num_keypoints, len(pts)), replace=False)]
+            keys.append(select_keypoints(sample, xyz, voxel_size, device=dev))
+        f0 = feat[0][torch.as_tensor(keys[0], device=dev)].float().contiguous()
+        f1 = feat[1][torch.as_tensor(keys[1], device=dev)].float().contiguous()
+        T = ransac_registration(down[0][keys[0]], down[1][keys[1]], nn_search(f0, f1), ransac_n=3, max_corr_dist=r,
+                                edge_similarity=0.9, max_iter=ransac_iter, seed=seed, device=dev)[0]
+        timed("global", t0)
+
+    t0 = time.time()
+    if refine == "plane":
+        normals, _ = estimate_normals(down[1], knn=30, max_radius=4.0 * voxel_size, viewpoint=np.zeros(3), device=dev)
+        timed("normals", t0)
+        t0 = time.time()
+        T, fitness, rmse, iters, n_corr = icp_point_to_plane(down[0], down[1], normals, r, init=T, device=dev)
+    elif refine == "point":
+        T, fitness, rmse, iters, n_corr = icp_point_to_point(down[0], down[1], r, init=T, max_iteration=30, device=dev)
+    else:                                                 # the statistics of the unrefined pose: one correspondence stage
+        T, fitness, rmse, iters, n_corr = icp_point_to_point(down[0], down[1], r, init=T, max_iteration=0, device=dev)
+    timed("refine", t0)
+    return dict(T=T, fitness=fitness, rmse=rmse, iterations=iters, n_corr=n_corr, times=times)
+
+
+def make_parser():
+    ap = argparse.ArgumentParser(prog="python -m imfnet_amd.register", description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--source", required=True, help="source fragment (.ply)")
+    ap.add_argument("--source_image", required=True)
+    ap.add_argument("--target", required=True, help="target fragment (.ply)")
+    ap.add_argument("--target_image", required=True)
+    ap.add_argument("-m", "--model", default=None, help="checkpoint (.pth); default: seeded weights")
+    ap.add_argument("--voxel_size", type=float, default=0.025)
+    ap.add_argument("--num_keypoints", type=int, default=5000)
+    ap.add_argument("--ransac_iter", type=int, default=50000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--init", default=None, help="4x4 text matrix the refinement starts from with --skip_global")
+    ap.add_argument("--skip_global", action="store_true", help="no RANSAC: refine from --init (identity when absent)")
+    ap.add_argument("--refine", choices=REFINE_CHOICES, default="plane")
+    ap.add_argument("--out", default=None, help="write the 4x4 source->target matrix here")
+    ap.add_argument("--device", default="cuda")
+    return ap
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    from .dataio import read_ply_points
+    model, cfg = load_network(args.model, torch.device(args.device))
+    init = np.loadtxt(args.init, dtype=np.float64).reshape(4, 4) if args.init else None
+    res = register_pair(model, cfg, read_ply_points(args.source), load_image(args.source_image, cfg),
+                        read_ply_points(args.target), load_image(args.target_image, cfg), voxel_size=args.voxel_size,
+                        num_keypoints=args.num_keypoints, ransac_iter=args.ransac_iter, seed=args.seed, init=init,
+                        skip_global=args.skip_global, refine=args.refine, device=args.device)
+    if args.out:
+        np.savetxt(args.out, res["T"], fmt="%.17g")
+    print(json.dumps(dict(fitness=res["fitness"], rmse=res["rmse"], iterations=res["iterations"], n_corr=res["n_corr"],
+                          times={k: round(v, 6) for k, v in res["times"].items()}, T=res["T"].tolist())))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -906,6 +906,31 @@ size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst);
 int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
                            const double *init_host, int max_iteration, double *out_T, double *out_stats,
                            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+/* imf_icp_point_to_plane.  Replaces: Open3D registration_icp(src, dst, max_corr_dist, init,
+ * TransformationEstimationPointToPlane(), ICPConvergenceCriteria(max_iteration)) on a target with normals (nothing upstream
+ * calls it; it is the refinement of imfnet_amd/register.py).  Everything of imf_icp_point_to_point holds -- the loop, the
+ * correspondence rule, fitness, rmse over point distances, the stop rule, the outputs, 2 (max_iteration + 1) + 5 launches,
+ * bit-identical runs -- except the update: r = (p - q) . n_q, J = [p x n_q, n_q], (sum J^T J) x = -(sum J^T r) by LDL^T,
+ * update = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5].  dst_normals: device fp64 [n_dst,3], row j the normal of dst row j.  The
+ * singular rule: a pivot <= 1e-12 times the largest diagonal entry of sum J^T J (a single-plane target, fewer than 6
+ * independent rows) makes the update the identity.  workspace: imf_icp_plane_workspace_bytes, 256-byte aligned. */
+size_t imf_icp_plane_workspace_bytes(int64_t n_src, int64_t n_dst);
+int imf_icp_point_to_plane(const double *src, int64_t n_src, const double *dst, const double *dst_normals, int64_t n_dst,
+                           double max_corr_dist, const double *init_host, int max_iteration, double *out_T,
+                           double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+/* imf_estimate_normals.  Replaces: o3d.geometry.PointCloud.estimate_normals with its default KDTreeSearchParamKNN(knn=30)
+ * (data/fuse_fragments_3DMatch.py:89), exactly (the rules are stated in csrc/normals.hip).  points: device fp64 [n,3];
+ * 1 <= knn <= 64; max_radius finite and > 0: the neighbour set of point i is the knn smallest of (d^2, index) among the
+ * points with d^2 <= max_radius^2, itself included; viewpoint_host: HOST double[3] or NULL.  Outputs (device): normals fp64
+ * [n,3], the unit eigenvector of the smallest eigenvalue of the set's two-pass covariance ((0,0,1) for fewer than 3 points),
+ * signed so that n . (viewpoint - p) >= 0, or with its largest component positive when viewpoint is NULL; counts int32 [n],
+ * the size of every set; nbr: optional int32 [n,knn], the sets in (d^2, index) order padded with -1; out_err int32[1], 1 if
+ * a point was NaN / out of the grid's range (cell edge max_radius / 2).  5 launches, no host synchronisation, no
+ * floating-point atomics: bit-identical from run to run.  workspace: imf_normals_workspace_bytes(n), 256-byte aligned. */
+size_t imf_normals_workspace_bytes(int64_t n);
+int imf_estimate_normals(const double *points, int64_t n, int knn, double max_radius, const double *viewpoint_host,
+                         double *normals, int32_t *counts, int32_t *nbr, int32_t *out_err, void *workspace,
+                         size_t workspace_bytes, void *stream);
 /* imf_radius_count replaces len(get_matching_indices(pcd0, pcd1, trans, r)) of util/pointcloud.py:56-69 (the
  * KITTI evaluator's "fewer than 1000 matches" skip, lib/data_loaders.py:586-588): the number of pairs (i, j) with
  * |T src_i - dst_j| <= r.  T_host: HOST 16 doubles row-major or NULL = identity.  out_count: device int64[1];
