@@ -103,6 +103,17 @@ def sparse_tensor_from_points(xyz, voxel_size, device, feats=None, before_sync=N
     return st, inds
 
 
+def voxel_representatives(xyz, voxel_size, device=None):
+    """The xyz_down `extract_features` returns for these points and this voxel size (every voxel's first point, in the
+    voxel order of the level-0 map), without a network: float64 numpy [M, 3]."""
+    device = _cuda_device(torch.device('cuda:0') if device is None else device)
+    _, inds = sparse_tensor_from_points(xyz, voxel_size, device)
+    if torch.is_tensor(xyz) and xyz.is_cuda:
+        return xyz.detach()[inds.long()].cpu().numpy().astype(np.float64)
+    host = xyz.detach().numpy() if torch.is_tensor(xyz) else np.asarray(xyz)
+    return host[inds.cpu().numpy().astype(np.int64)].astype(np.float64, copy=False)
+
+
 def _host_inputs(xyz, image):
     """(points as a host float32 / float64 array, image as a host float32 array), or None when either lives on the GPU."""
     if (torch.is_tensor(xyz) and xyz.is_cuda) or (torch.is_tensor(image) and image.is_cuda):

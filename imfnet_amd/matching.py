@@ -233,6 +233,41 @@ def estimate_normals(points, knn=30, max_radius=0.1, viewpoint=None, device="cud
     return out + (nbr.cpu().numpy(),) if return_neighbors else out
 
 
+def compute_fpfh(points, normals=None, radius=0.125, max_nn=64, normal_knn=30, normal_radius=None, viewpoint=None,
+                 width=33, device="cuda", return_hist=False):
+    """o3d.pipelines.registration.compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) on the device
+    (imf_fpfh_features; the rules are stated in csrc/fpfh.hip): the 33-bin Fast Point Feature Histogram of every point
+    over its max_nn nearest cloud points within radius, the lists being `estimate_normals(points, knn=max_nn,
+    max_radius=radius, return_neighbors=True)`.  normals: [n, 3], or None = `estimate_normals(knn=normal_knn,
+    max_radius=normal_radius or radius, viewpoint=viewpoint)`.  width: 33, or 64 = zero-padded to a width `nn_search`
+    takes (the distances are the same).  Returns a float32 device tensor [n, width] and, with return_hist=True, the int32
+    device tensor [n, 33] of the SPFH pair counts."""
+    if not 1 <= int(max_nn) <= 64:
+        raise ImfError(f"compute_fpfh: max_nn={max_nn}, expected 1..64")
+    if width not in (33, 64):
+        raise ImfError(f"compute_fpfh: width={width}, expected 33 or 64")
+    p = _points(points, device, "points")
+    n = p.shape[0]
+    _, counts, nbr = estimate_normals(p, knn=int(max_nn), max_radius=radius, device=p.device, return_neighbors=True)
+    if normals is None:
+        normals, _ = estimate_normals(p, knn=normal_knn, max_radius=normal_radius or radius, viewpoint=viewpoint,
+                                      device=p.device)
+    nrm = _points(normals, p.device, "normals")
+    if nrm.shape != p.shape:
+        raise ImfError(f"compute_fpfh: normals {tuple(nrm.shape)} for points {tuple(p.shape)}")
+    nbr = torch.as_tensor(nbr).to(p.device).contiguous()
+    counts = torch.as_tensor(counts).to(p.device).contiguous()
+    L = _lib.lib()
+    nbytes = L.imf_fpfh_workspace_bytes(n, int(max_nn))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty((n, width), dtype=torch.float32, device=p.device)
+    hist = torch.empty((n, 33), dtype=torch.int32, device=p.device) if return_hist else None
+    check(L.imf_fpfh_features(p.data_ptr(), nrm.data_ptr(), n, nbr.data_ptr(), counts.data_ptr(), int(max_nn), int(width),
+                              out.data_ptr(), hist.data_ptr() if return_hist else None, ws.data_ptr(), nbytes, _stream()),
+          "imf_fpfh_features")
+    return (out, hist) if return_hist else out
+
+
 def radius_count(src, dst, T=None, r=0.45, per_point=False, device="cuda"):
     """len(get_matching_indices(src, dst, T, r)) of util/pointcloud.py:56-69: the number of pairs (i, j) with
     |T src_i - dst_j| <= r (imf_radius_count).  Returns the int count, or (count, int32 numpy [n_src] per-point

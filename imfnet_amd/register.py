@@ -2,6 +2,7 @@
 
     python -m imfnet_amd.register --source A.ply --source_image A.png --target B.ply --target_image B.png
                                   [-m checkpoint.pth] [--refine plane] [--out T.txt]
+    python -m imfnet_amd.register --descriptor fpfh --source A.ply --target B.ply
 
 The stages are the library's own, in the order scripts/evaluation_3dmatch.py and scripts/benchmark_util.py use them:
 `extract_features` on both fragments, the keypoint draw (`num_keypoints` raw points without replacement from
@@ -10,6 +11,9 @@ RandomState(seed), source first) and `select_keypoints`, RANSAC on the nearest-d
 against the target's `estimate_normals(knn=30, max_radius=4 voxel, viewpoint=origin)`.  --skip_global starts the
 refinement from --init (identity when absent); the descriptors are still extracted.  Without -m the network runs on
 the seeded weights of the test oracle: the global stage is then meaningless, the plumbing is the same.
+--descriptor fpfh needs neither a checkpoint nor the images (they are not read): the descriptors are `compute_fpfh` on the
+voxel representatives (radius 5 voxel, max_nn 64, normals at 2 voxel facing the origin, zero-padded to 64 columns); the
+keypoints, RANSAC and the refinement are the same.
 
 Writes the 4x4 source->target matrix to --out (np.savetxt) and prints one JSON line: fitness, rmse, iterations, n_corr,
 the stage times in seconds and the matrix.
@@ -25,6 +29,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFINE_CHOICES = ("none", "point", "plane")
+DESCRIPTOR_CHOICES = ("imfnet", "fpfh")
 
 
 def load_network(checkpoint, device):
@@ -53,15 +58,27 @@ def load_image(path, cfg):
     return image_to_nchw(img)
 
 
+def fpfh_descriptors(xyz_down, voxel_size, device="cuda"):
+    """The FPFH descriptors of voxel representatives as this command and imfnet_amd.fpfh_desc compute them: float32 device
+    tensor [M, 64], columns 33.. zero."""
+    from .matching import compute_fpfh
+    return compute_fpfh(xyz_down, radius=5.0 * voxel_size, max_nn=64, normal_knn=30, normal_radius=2.0 * voxel_size,
+                        viewpoint=np.zeros(3), width=64, device=device)
+
+
 def register_pair(model, cfg, source, source_image, target, target_image, voxel_size=0.025, num_keypoints=5000,
-                  ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda"):
-    """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  Returns
-    dict(T 4x4 numpy source->target, fitness, rmse, iterations, n_corr, times)."""
-    from .extract import extract_features
-    from .matching import (estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search, ransac_registration,
-                           select_keypoints)
+                  ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda",
+                  descriptor="imfnet"):
+    """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  With
+    descriptor="fpfh" model, cfg and the images are not used (None will do).  Returns dict(T 4x4 numpy source->target,
+    fitness, rmse, iterations, n_corr, times)."""
+    from .extract import extract_features, voxel_representatives
+    from .matching import (compute_fpfh, estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search,
+                           ransac_registration, select_keypoints)
     if refine not in REFINE_CHOICES:
         raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
+    if descriptor not in DESCRIPTOR_CHOICES:
+        raise ValueError(f"descriptor must be one of {DESCRIPTOR_CHOICES}, got {descriptor!r}")
     dev = torch.device(device)
     times = {}
 
@@ -73,8 +90,12 @@ def register_pair(model, cfg, source, source_image, target, target_image, voxel_
     down, feat = [], []
     with torch.no_grad():
         for pts, img in ((source, source_image), (target, target_image)):
-            xyz, F = extract_features(model, np.asarray(pts, np.float64), voxel_size=voxel_size, device=dev,
-                                      skip_check=True, image=img)
+            if descriptor == "fpfh":
+                xyz = voxel_representatives(np.asarray(pts, np.float64), voxel_size, dev)
+                F = fpfh_descriptors(xyz, voxel_size, dev)
+            else:
+                xyz, F = extract_features(model, np.asarray(pts, np.float64), voxel_size=voxel_size, device=dev,
+                                          skip_check=True, image=img)
             down.append(np.asarray(xyz, np.float64))
             feat.append(F)
     timed("features", t0)
@@ -113,9 +134,11 @@ def make_parser():
     ap = argparse.ArgumentParser(prog="python -m imfnet_amd.register", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--source", required=True, help="source fragment (.ply)")
-    ap.add_argument("--source_image", required=True)
+    ap.add_argument("--source_image", default=None, help="required with --descriptor imfnet; not read with fpfh")
     ap.add_argument("--target", required=True, help="target fragment (.ply)")
-    ap.add_argument("--target_image", required=True)
+    ap.add_argument("--target_image", default=None, help="required with --descriptor imfnet; not read with fpfh")
+    ap.add_argument("--descriptor", choices=DESCRIPTOR_CHOICES, default="imfnet",
+                    help="imfnet: the network's descriptors; fpfh: hand-crafted, no checkpoint and no images")
     ap.add_argument("-m", "--model", default=None, help="checkpoint (.pth); default: seeded weights")
     ap.add_argument("--voxel_size", type=float, default=0.025)
     ap.add_argument("--num_keypoints", type=int, default=5000)
@@ -130,14 +153,21 @@ def make_parser():
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    ap = make_parser()
+    args = ap.parse_args(argv)
     from .dataio import read_ply_points
-    model, cfg = load_network(args.model, torch.device(args.device))
+    if args.descriptor == "fpfh":
+        model = cfg = src_image = dst_image = None
+    else:
+        if args.source_image is None or args.target_image is None:
+            ap.error("--source_image and --target_image are required with --descriptor imfnet")
+        model, cfg = load_network(args.model, torch.device(args.device))
+        src_image, dst_image = load_image(args.source_image, cfg), load_image(args.target_image, cfg)
     init = np.loadtxt(args.init, dtype=np.float64).reshape(4, 4) if args.init else None
-    res = register_pair(model, cfg, read_ply_points(args.source), load_image(args.source_image, cfg),
-                        read_ply_points(args.target), load_image(args.target_image, cfg), voxel_size=args.voxel_size,
-                        num_keypoints=args.num_keypoints, ransac_iter=args.ransac_iter, seed=args.seed, init=init,
-                        skip_global=args.skip_global, refine=args.refine, device=args.device)
+    res = register_pair(model, cfg, read_ply_points(args.source), src_image, read_ply_points(args.target), dst_image,
+                        voxel_size=args.voxel_size, num_keypoints=args.num_keypoints, ransac_iter=args.ransac_iter,
+                        seed=args.seed, init=init, skip_global=args.skip_global, refine=args.refine, device=args.device,
+                        descriptor=args.descriptor)
     if args.out:
         np.savetxt(args.out, res["T"], fmt="%.17g")
     print(json.dumps(dict(fitness=res["fitness"], rmse=res["rmse"], iterations=res["iterations"], n_corr=res["n_corr"],

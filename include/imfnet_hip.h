@@ -931,6 +931,19 @@ size_t imf_normals_workspace_bytes(int64_t n);
 int imf_estimate_normals(const double *points, int64_t n, int knn, double max_radius, const double *viewpoint_host,
                          double *normals, int32_t *counts, int32_t *nbr, int32_t *out_err, void *workspace,
                          size_t workspace_bytes, void *stream);
+/* imf_fpfh_features.  Replaces: nothing upstream; Open3D's compute_fpfh_feature (Rusu 2009) restated -- the rules, and
+ * which of them are recalled rather than checked, are stated in csrc/fpfh.hip.  The entry does not search: nbr int32
+ * [n,knn] and counts int32 [n] are the lists imf_estimate_normals wrote for the same points (the point itself included,
+ * padded with -1); entries equal to i or outside [0, n) are skipped.  points, normals: device fp64 [n,3]; 1 <= n < 2^30;
+ * 1 <= knn <= 64; width 33 or 64.  Outputs (device): out fp32 [n,width], the 33 FPFH bins (three groups of 11, each
+ * summing to 200, or to 100 where no neighbour is at d^2 > 0) and +0.0f in columns 33..; out_hist: optional int32 [n,33],
+ * the integer SPFH pair counts (rows sum to 3 m_i).  fp64 throughout without fused multiply-add, one rounding to fp32.
+ * 2 launches, no host synchronisation, no atomics: bit-identical from run to run.  workspace:
+ * imf_fpfh_workspace_bytes(n, knn) (0 for arguments out of range), 256-byte aligned. */
+size_t imf_fpfh_workspace_bytes(int64_t n, int knn);
+int imf_fpfh_features(const double *points, const double *normals, int64_t n, const int32_t *nbr, const int32_t *counts,
+                      int knn, int width, float *out, int32_t *out_hist, void *workspace, size_t workspace_bytes,
+                      void *stream);
 /* imf_radius_count replaces len(get_matching_indices(pcd0, pcd1, trans, r)) of util/pointcloud.py:56-69 (the
  * KITTI evaluator's "fewer than 1000 matches" skip, lib/data_loaders.py:586-588): the number of pairs (i, j) with
  * |T src_i - dst_j| <= r.  T_host: HOST 16 doubles row-major or NULL = identity.  out_count: device int64[1];
