@@ -292,6 +292,8 @@ SIGNATURES = {
     "imf_estimate_normals": (_I, [_P, _L, _I, _D, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "imf_fpfh_workspace_bytes": (_Z, [_L, _I]),
     "imf_fpfh_features": (_I, [_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    "imf_information_workspace_bytes": (_Z, [_L, _L]),
+    "imf_information_matrix": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _P, _Z, _P]),
     "imf_radius_count_workspace_bytes": (_Z, [_L]),
     "imf_radius_count": (_I, [_P, _L, _P, _L, _P, _D, _P, _P, _P, _P, _Z, _P]),
     "imf_radius_pairs_workspace_bytes": (_Z, [_L, _L]),

@@ -97,43 +97,6 @@ struct IcpState {
   int32_t n_corr, iters, done, pad;
 };
 
-// nearest target (d^2 < r2, ties -> lowest original index) of p; returns its sorted row or -1
-__device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, double &best_d2) {
-  int x, y, z;
-  best_d2 = 0.0;
-  if (!cell_of_point(p, g.inv_cell, kCoordLim, x, y, z)) return -1;   // beyond every target cell's neighbourhood
-  int best = -1, best_idx = 0x7FFFFFFF;
-  double bd = r2;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int s = hash_find_slot(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
-        if (s < 0) continue;
-        const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
-        const int r0 = (int)v.z, r1 = r0 + (int)v.w;
-        for (int r = r0; r < r1; ++r) {
-          const V3 e = sub(load3(g.xyz, r), p);
-          const double d2 = dot(e, e);
-          const int id = g.idx[r];
-          if (d2 < bd || (d2 == bd && best >= 0 && id < best_idx)) {
-            bd = d2; best = r; best_idx = id;
-          }
-        }
-      }
-  best_d2 = bd;
-  return best;
-}
-
-// fixed-order sum of a workgroup's per-thread values (xor butterfly per wavefront, then the 4 wavefronts in order)
-__device__ __forceinline__ double block_sum(double v, double *lds4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) lds4[w] = v;
-  __syncthreads();
-  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-}
-
 __global__ __launch_bounds__(256) void k_icp_start(const double *__restrict__ src, int64_t n, IcpInit init,
                                                    double *__restrict__ cur, IcpState *st) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,6 +1,8 @@
 // The cell-CSR grid over a point set that the ICPs, the radius searches (icp.hip) and the k-NN normals (normals.hip)
 // search.  The rules are documented at the head of icp.hip: cell = floor(x * inv_cell) with inv_cell = (1 - 1e-9) / edge,
 // 18-bit keys per axis, targets one cell inside the key range, an out-of-range or NaN target raises the error flag.
+// grid_nearest is the one correspondence rule of the ICPs and of the information matrix (information.hip); block_sum is
+// their fixed-order workgroup sum.
 // Everything here has internal linkage: each translation unit that includes it gets its own kernels.
 #pragma once
 #include "common.h"
@@ -87,6 +89,43 @@ __global__ __launch_bounds__(256) void k_grid_scatter(const double *__restrict__
   g.xyz[3 * (int64_t)r + 1] = dst[3 * j + 1];
   g.xyz[3 * (int64_t)r + 2] = dst[3 * j + 2];
   g.idx[r] = (int32_t)j;
+}
+
+// nearest target (d^2 < r2, ties -> lowest original index) of p; returns its sorted row or -1
+__device__ __forceinline__ int grid_nearest(const Grid &g, V3 p, double r2, double &best_d2) {
+  int x, y, z;
+  best_d2 = 0.0;
+  if (!cell_of_point(p, g.inv_cell, kCoordLim, x, y, z)) return -1;   // beyond every target cell's neighbourhood
+  int best = -1, best_idx = 0x7FFFFFFF;
+  double bd = r2;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int s = hash_find_slot(g.tab, g.capmask, pack_key(0, x + dx, y + dy, z + dz));
+        if (s < 0) continue;
+        const uint4 v = *reinterpret_cast<const uint4 *>(g.tab + s);
+        const int r0 = (int)v.z, r1 = r0 + (int)v.w;
+        for (int r = r0; r < r1; ++r) {
+          const V3 e = sub(load3(g.xyz, r), p);
+          const double d2 = dot(e, e);
+          const int id = g.idx[r];
+          if (d2 < bd || (d2 == bd && best >= 0 && id < best_idx)) {
+            bd = d2; best = r; best_idx = id;
+          }
+        }
+      }
+  best_d2 = bd;
+  return best;
+}
+
+// fixed-order sum of a workgroup's per-thread values (xor butterfly per wavefront, then the 4 wavefronts in order)
+__device__ __forceinline__ double block_sum(double v, double *lds4) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) lds4[w] = v;
+  __syncthreads();
+  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
 }
 
 // workspace layout of the grid (all offsets 256-byte aligned)

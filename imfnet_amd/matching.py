@@ -205,6 +205,29 @@ def icp_point_to_plane(src, dst, dst_normals, max_corr_dist, init=None, max_iter
     return _icp("icp_point_to_plane", src, dst, dst_normals, max_corr_dist, init, max_iteration, device)
 
 
+def information_matrix(src, dst, T=None, max_corr_dist=0.0375, device="cuda"):
+    """Open3D get_information_matrix_from_point_clouds(src, dst, max_corr_dist, T) on the device (imf_information_matrix;
+    the rules are restated in csrc/information.hip): the sum of G^T G over ICP's correspondences of T . src in dst, G =
+    [-[q]x | I] of the target point q, rotation first -- the matrix of a gt.info record and the weight of a pose-graph
+    edge.  Returns (6x6 float64 numpy, exactly symmetric, the number of correspondences)."""
+    s = _points(src, device, "src")
+    d = _points(dst, s.device, "dst")
+    L = _lib.lib()
+    nbytes = L.imf_information_workspace_bytes(s.shape[0], d.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    info = torch.empty(36, dtype=torch.float64, device=s.device)
+    meta = torch.zeros(2, dtype=torch.int32, device=s.device)
+    Th = _host_T(T)
+    check(L.imf_information_matrix(s.data_ptr(), s.shape[0], d.data_ptr(), d.shape[0],
+                                   Th.ctypes.data_as(C.c_void_p) if Th is not None else None, float(max_corr_dist),
+                                   info.data_ptr(), meta.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "imf_information_matrix")
+    n_corr, err = meta.tolist()
+    if err:
+        raise ImfError("information_matrix: a target point is NaN or beyond the grid's range")
+    return info.cpu().numpy().reshape(6, 6), n_corr
+
+
 def estimate_normals(points, knn=30, max_radius=0.1, viewpoint=None, device="cuda", return_neighbors=False):
     """o3d.geometry.PointCloud.estimate_normals(KDTreeSearchParamKNN(knn)) on the device, exactly (imf_estimate_normals;
     the rules are stated in csrc/normals.hip): the PCA normal of every point's knn nearest cloud points within max_radius,

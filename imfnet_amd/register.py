@@ -66,39 +66,39 @@ def fpfh_descriptors(xyz_down, voxel_size, device="cuda"):
                         viewpoint=np.zeros(3), width=64, device=device)
 
 
-def register_pair(model, cfg, source, source_image, target, target_image, voxel_size=0.025, num_keypoints=5000,
-                  ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda",
-                  descriptor="imfnet"):
-    """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  With
-    descriptor="fpfh" model, cfg and the images are not used (None will do).  Returns dict(T 4x4 numpy source->target,
-    fitness, rmse, iterations, n_corr, times)."""
+def fragment_features(model, cfg, points, image, voxel_size=0.025, device="cuda", descriptor="imfnet"):
+    """One fragment's voxel representatives and their descriptors: (xyz_down float64 numpy [M, 3], device tensor [M, C]).
+    With descriptor="fpfh" model, cfg and image are not used."""
     from .extract import extract_features, voxel_representatives
-    from .matching import (compute_fpfh, estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search,
-                           ransac_registration, select_keypoints)
-    if refine not in REFINE_CHOICES:
-        raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
     if descriptor not in DESCRIPTOR_CHOICES:
         raise ValueError(f"descriptor must be one of {DESCRIPTOR_CHOICES}, got {descriptor!r}")
     dev = torch.device(device)
-    times = {}
+    with torch.no_grad():
+        if descriptor == "fpfh":
+            xyz = voxel_representatives(np.asarray(points, np.float64), voxel_size, dev)
+            F = fpfh_descriptors(xyz, voxel_size, dev)
+        else:
+            xyz, F = extract_features(model, np.asarray(points, np.float64), voxel_size=voxel_size, device=dev,
+                                      skip_check=True, image=image)
+    return np.asarray(xyz, np.float64), F
+
+
+def register_features(source, target, down, feat, voxel_size=0.025, num_keypoints=5000, ransac_iter=50000, seed=0,
+                      init=None, skip_global=False, refine="plane", device="cuda", times=None, target_normals=None):
+    """The keypoint draw, RANSAC and the refinement on two fragments' features.  source / target: the raw points; down,
+    feat: (source's, target's) `fragment_features`.  target_normals: the target's `estimate_normals(knn=30, max_radius=4
+    voxel, viewpoint=origin)` when the caller holds them (refine="plane"), else computed here.  times: a dict that receives
+    the stage times.  Returns dict(T 4x4 numpy source->target, fitness, rmse, iterations, n_corr, times)."""
+    from .matching import (estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search, ransac_registration,
+                           select_keypoints)
+    if refine not in REFINE_CHOICES:
+        raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
+    dev = torch.device(device)
+    times = {} if times is None else times
 
     def timed(name, t0):
         torch.cuda.synchronize(dev)
         times[name] = time.time() - t0
-
-    t0 = time.time()
-    down, feat = [], []
-    with torch.no_grad():
-        for pts, img in ((source, source_image), (target, target_image)):
-            if descriptor == "fpfh":
-                xyz = voxel_representatives(np.asarray(pts, np.float64), voxel_size, dev)
-                F = fpfh_descriptors(xyz, voxel_size, dev)
-            else:
-                xyz, F = extract_features(model, np.asarray(pts, np.float64), voxel_size=voxel_size, device=dev,
-                                          skip_check=True, image=img)
-            down.append(np.asarray(xyz, np.float64))
-            feat.append(F)
-    timed("features", t0)
 
     r = 1.5 * voxel_size
     T = np.eye(4) if init is None else np.asarray(init, np.float64).reshape(4, 4)
@@ -118,7 +118,9 @@ def register_pair(model, cfg, source, source_image, target, target_image, voxel_
 
     t0 = time.time()
     if refine == "plane":
-        normals, _ = estimate_normals(down[1], knn=30, max_radius=4.0 * voxel_size, viewpoint=np.zeros(3), device=dev)
+        normals = target_normals
+        if normals is None:
+            normals, _ = estimate_normals(down[1], knn=30, max_radius=4.0 * voxel_size, viewpoint=np.zeros(3), device=dev)
         timed("normals", t0)
         t0 = time.time()
         T, fitness, rmse, iters, n_corr = icp_point_to_plane(down[0], down[1], normals, r, init=T, device=dev)
@@ -128,6 +130,31 @@ def register_pair(model, cfg, source, source_image, target, target_image, voxel_
         T, fitness, rmse, iters, n_corr = icp_point_to_point(down[0], down[1], r, init=T, max_iteration=0, device=dev)
     timed("refine", t0)
     return dict(T=T, fitness=fitness, rmse=rmse, iterations=iters, n_corr=n_corr, times=times)
+
+
+def register_pair(model, cfg, source, source_image, target, target_image, voxel_size=0.025, num_keypoints=5000,
+                  ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda",
+                  descriptor="imfnet"):
+    """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  With
+    descriptor="fpfh" model, cfg and the images are not used (None will do).  Returns dict(T 4x4 numpy source->target,
+    fitness, rmse, iterations, n_corr, times)."""
+    if refine not in REFINE_CHOICES:
+        raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
+    if descriptor not in DESCRIPTOR_CHOICES:
+        raise ValueError(f"descriptor must be one of {DESCRIPTOR_CHOICES}, got {descriptor!r}")
+    dev = torch.device(device)
+    times = {}
+    t0 = time.time()
+    down, feat = [], []
+    for pts, img in ((source, source_image), (target, target_image)):
+        xyz, F = fragment_features(model, cfg, pts, img, voxel_size=voxel_size, device=dev, descriptor=descriptor)
+        down.append(xyz)
+        feat.append(F)
+    torch.cuda.synchronize(dev)
+    times["features"] = time.time() - t0
+    return register_features(source, target, down, feat, voxel_size=voxel_size, num_keypoints=num_keypoints,
+                             ransac_iter=ransac_iter, seed=seed, init=init, skip_global=skip_global, refine=refine,
+                             device=dev, times=times)
 
 
 def make_parser():

@@ -944,6 +944,20 @@ size_t imf_fpfh_workspace_bytes(int64_t n, int knn);
 int imf_fpfh_features(const double *points, const double *normals, int64_t n, const int32_t *nbr, const int32_t *counts,
                       int knn, int width, float *out, int32_t *out_hist, void *workspace, size_t workspace_bytes,
                       void *stream);
+/* imf_information_matrix.  Replaces: nothing upstream computes it; it is the 6x6 matrix of a 3DMatch gt.info record, Open3D's
+ * GetInformationMatrixFromPointClouds(source, target, max_corr_dist, T) restated -- the rules, recalled rather than checked,
+ * are stated in csrc/information.hip.  Every source point p = T src_s takes imf_icp_point_to_point's correspondence (nearest
+ * target with d^2 < max_corr_dist^2, strict; ties -> lowest target index; the same grid), and each correspondence adds G^T G
+ * with G = [-[q]x | I] of the TARGET point q (rotation first).  src [n_src,3], dst [n_dst,3]: device fp64; T_host: HOST 16
+ * doubles row-major or NULL = identity.  Outputs (device): out_info double[36], row-major, exactly symmetric, entries [3,3] =
+ * [4,4] = [5,5] = the number of correspondences, 36 times +0.0 without any; out_meta int32[2] = {correspondences, 1 if a
+ * target point was NaN / out of the grid's range}.  6 launches, no host synchronisation, fp64 without fused multiply-add in
+ * the sums, no floating-point atomics: bit-identical from run to run.  workspace: imf_information_workspace_bytes(n_src,
+ * n_dst) (0 for arguments out of range), 256-byte aligned. */
+size_t imf_information_workspace_bytes(int64_t n_src, int64_t n_dst);
+int imf_information_matrix(const double *src, int64_t n_src, const double *dst, int64_t n_dst, const double *T_host,
+                           double max_corr_dist, double *out_info, int32_t *out_meta, void *workspace,
+                           size_t workspace_bytes, void *stream);
 /* imf_radius_count replaces len(get_matching_indices(pcd0, pcd1, trans, r)) of util/pointcloud.py:56-69 (the
  * KITTI evaluator's "fewer than 1000 matches" skip, lib/data_loaders.py:586-588): the number of pairs (i, j) with
  * |T src_i - dst_j| <= r.  T_host: HOST 16 doubles row-major or NULL = identity.  out_count: device int64[1];

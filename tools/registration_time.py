@@ -5,8 +5,9 @@
 
 estimate_normals(target, knn 30, 10 cm, viewpoint at the origin) and the point-to-plane / point-to-point ICP calls at
 r = 3.75 cm from a 4 degree / 2.4 cm start, at max_iteration 0 (the grid and one correspondence stage) and 1 (one more
-stage and one update).  Each figure is the median of --reps calls after a warm-up, host clock around a call that takes
-device tensors and ends with its results on the host; `iteration` is the difference of the two medians."""
+stage and one update), and information_matrix on the same pair, radius and start.  Each figure
+is the median of --reps calls after a warm-up, host clock around a call that takes device tensors and ends with its
+results on the host; `iteration` is the difference of the two medians."""
 import argparse
 import json
 import os
@@ -44,7 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     a = ap.parse_args()
-    from imfnet_amd.matching import estimate_normals, icp_point_to_plane, icp_point_to_point
+    from imfnet_amd.matching import estimate_normals, icp_point_to_plane, icp_point_to_point, information_matrix
     z = np.load(os.path.join(ROOT, "tests", "golden", "fixture_clouds.npz"))
     src = voxel_reps(z["cloud_bin_0"].astype(np.float64), 0.025)
     dst = voxel_reps(z["cloud_bin_1"].astype(np.float64), 0.025)
@@ -62,6 +63,8 @@ def main():
         t0, t1 = timed(lambda: fn(0), a.reps), timed(lambda: fn(1), a.reps)
         res[name] = dict(max_iteration_0=t0, max_iteration_1=t1, iteration_ms=t1["median_ms"] - t0["median_ms"],
                          n_corr=int(fn(1)[4]), iterations_to_stop=int(fn(30)[3]))
+    res["information_matrix"] = dict(timed(lambda: information_matrix(src, dst, T=T, max_corr_dist=0.0375), a.reps),
+                                     n_corr=int(information_matrix(src, dst, T=T, max_corr_dist=0.0375)[1]))
     print(json.dumps(res, indent=1))
     return 0
 
