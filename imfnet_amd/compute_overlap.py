@@ -47,8 +47,9 @@ def fragment_number(stem):
 
 
 def list_fragments(folder):
-    """The stems of the folder's cloud_bin_*.ply, alphanumeric."""
+    """The stems of the folder's cloud_bin_*.ply, alphanumeric (without the cloud_bin_K.mesh.ply of fuse_fragments --mesh)."""
     names = [os.path.basename(p) for p in glob.glob(os.path.join(glob.escape(folder), "cloud_bin_*.ply"))]
+    names = [name for name in names if not name.endswith(".mesh.ply")]
     return [name[:-4] for name in sorted_alphanum(names)]
 
 

@@ -75,6 +75,51 @@ def read_ply_points_numpy(path):
     return np.stack([a["x"], a["y"], a["z"]], 1).astype(np.float64)
 
 
+def read_ply_mesh(path):
+    """(vertices float64 [N,3], triangles int32 [M,3]) of a binary little-endian PLY as fuse_fragments.write_ply_mesh
+    writes it: scalar vertex properties holding x, y, z, then `element face` with one `list uchar int` property whose
+    lists all have three entries."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, counts, props, element = None, {}, {"vertex": [], "face": []}, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                counts[element] = int(tok[2])
+                if element not in props or (element == "face" and "vertex" not in counts):
+                    raise ValueError(f"{path}: element {element} (expected vertex, then face)")
+            elif tok[0] == "property" and element is not None:
+                props[element].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: format {fmt} (read_ply_mesh reads binary_little_endian)")
+        if any(p[0] == "list" for p in props["vertex"]):
+            raise ValueError(f"{path}: list property in vertex element")
+        names = [p[1] for p in props["vertex"]]
+        if not all(a in names for a in "xyz"):
+            raise ValueError(f"{path}: vertex element has no x/y/z")
+        if "face" not in counts or len(props["face"]) != 1 or props["face"][0][:3] != ["list", "uchar", "int"]:
+            raise ValueError(f"{path}: the face element must hold one `list uchar int` property")
+        vdt = np.dtype([(nm, "<" + _PLY_TYPES[t]) for t, nm in props["vertex"]])
+        nv, nf = counts["vertex"], counts["face"]
+        v = np.frombuffer(f.read(nv * vdt.itemsize), dtype=vdt, count=nv)
+        fdt = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+        faces = np.frombuffer(f.read(nf * fdt.itemsize), dtype=fdt, count=nf)
+    if (faces["n"] != 3).any():
+        raise ValueError(f"{path}: a face that is no triangle")
+    return np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float64), np.ascontiguousarray(faces["v"], np.int32)
+
+
 def read_image(path):
     """matplotlib.image.imread semantics (generate_desc.py:92): PNG -> float32 in [0,1] (HWC, alpha
     dropped is NOT done by the reference; fixtures are RGB); any other format -> uint8 0..255, which the

@@ -1,4 +1,5 @@
-"""Fragment fusion on the GPU: depth frames -> sparse TSDF volume -> surface points (csrc/tsdf.hip).
+"""Fragment fusion on the GPU: depth frames -> sparse TSDF volume -> surface points (csrc/tsdf.hip) or a triangle mesh
+(csrc/tsdf_mesh.hip).
 
 Replaces what data/fuse_fragments_3DMatch.py:47-96 does with Open3D's `ScalableTSDFVolume`: `integrate` per frame and
 `extract_point_cloud`.  No colour, no normals (nothing downstream reads them).  There is no CPU path: a missing library or
@@ -40,7 +41,8 @@ def _depth_to_device(depth, device):
 class TSDFVolume:
     """A sparse TSDF volume in device memory.  `allocate` opens the 16^3-voxel units around the depth samples of a batch of
     frames (any number of calls, all before the first `integrate`), `integrate` folds a batch of frames into the running
-    average in frame order, `extract` returns the surface points as float64 [n,3] in a defined order.  Frames fed in
+    average in frame order, `extract` returns the surface points as float64 [n,3] in a defined order, `extract_mesh` the
+    surface as vertices and triangles; `voxels` / `load_voxels` save and restore the state.  Frames fed in
     several goes give the bits of one go.  lattice_offset: 0.5 samples the voxel centres (Open3D), 0 the voxel corners
     (the lattice the published 3DMatch fragments lie on)."""
 
@@ -147,14 +149,78 @@ class TSDFVolume:
         call(out, n)
         return out.cpu().numpy()
 
+    def extract_mesh(self):
+        """The surface as a triangle mesh (csrc/tsdf_mesh.hip: marching tetrahedra on the Kuhn split): vertices float64
+        [n,3] ordered by (unit, voxel, edge slot) and triangles int32 [m,3] ordered by (unit, cell, tetrahedron, triangle),
+        counter-clockwise seen from free space, on the host."""
+        none = np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int32)
+        if self._voxels is None or self.n_units == 0:
+            return none
+        dev, n_u = self.device, self.n_units
+        ws_bytes = self.L.imf_tsdf_mesh_workspace_bytes(n_u)
+        if ws_bytes == 0:
+            raise _lib.ImfError(f"imf_tsdf_mesh_workspace_bytes refuses {n_u} units")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out_n = torch.zeros(2, dtype=torch.int64, device=dev)
 
-def fuse_fragment(depth_u16, poses_cam2world, intrinsic, voxel_length=3.0 / 512, sdf_trunc=0.04, depth_scale=1000.0,
-                  depth_trunc=6.0, lattice_offset=0.5, device="cuda"):
-    """One fragment: depth_u16 [F,H,W] uint16, poses_cam2world [F,4,4], intrinsic [3,3] -> float64 [n,3]."""
+        def call(vertices, triangles):
+            rc = self.L.imf_tsdf_mesh(_ptr(self._voxels), _ptr(self._units), _ptr(self._meta), n_u, _ptr(self._table),
+                                      self.table_capacity, C.byref(self.params),
+                                      _ptr(vertices) if vertices is not None else None, 0 if vertices is None else len(vertices),
+                                      _ptr(triangles) if triangles is not None else None,
+                                      0 if triangles is None else len(triangles), _ptr(out_n), _ptr(ws), ws_bytes, _stream(dev))
+            _lib.check(rc, "imf_tsdf_mesh")
+
+        call(None, None)                                     # count, then the mesh into buffers of that size
+        n_v, n_t = out_n.tolist()
+        if n_v == 0 or n_t == 0:
+            return none
+        if n_v > 2 ** 31 - 1:
+            raise _lib.ImfError(f"TSDFVolume.extract_mesh: {n_v} vertices do not fit int32 indices")
+        vertices = torch.empty((n_v, 3), dtype=torch.float64, device=dev)
+        triangles = torch.empty((n_t, 3), dtype=torch.int32, device=dev)
+        call(vertices, triangles)
+        return vertices.cpu().numpy(), triangles.cpu().numpy()
+
+    def voxels(self):
+        """The state as a host copy: float32 [n_units, 4096, 2] = (tsdf, weight) of voxel (z * 16 + y) * 16 + x."""
+        if self._voxels is None or self.n_units == 0:
+            return np.zeros((self.n_units, UNIT_VOXELS, 2), np.float32)
+        return self._voxels[:self.n_units].cpu().numpy()
+
+    def load_voxels(self, array):
+        """Replaces the state with float32 [n_units, 4096, 2] (what `voxels` returns).  Allowed once the unit rows are
+        final, that is after `allocate`; like `integrate` it ends the allocation phase."""
+        a = np.ascontiguousarray(array, np.float32)
+        if a.shape != (self.n_units, UNIT_VOXELS, 2):
+            raise ValueError(f"voxels must be [{self.n_units}, {UNIT_VOXELS}, 2], got {a.shape}")
+        if self.n_units == 0:
+            raise _lib.ImfError("TSDFVolume.load_voxels: no units are open (call allocate first)")
+        self._pending = []
+        self._voxels = torch.from_numpy(a).to(self.device).contiguous()
+
+
+def fuse_volume(depth_u16, poses_cam2world, intrinsic, voxel_length=3.0 / 512, sdf_trunc=0.04, depth_scale=1000.0,
+                depth_trunc=6.0, lattice_offset=0.5, device="cuda"):
+    """The volume of one fragment, allocated and integrated."""
     depth = depth_u16 if isinstance(depth_u16, torch.Tensor) else np.asarray(depth_u16)
     vol = TSDFVolume(intrinsic, depth.shape[1], depth.shape[2], voxel_length, sdf_trunc, depth_scale, depth_trunc,
                      lattice_offset, device)
     d = _depth_to_device(depth, vol.device)
     vol.allocate(d, poses_cam2world)
     vol.integrate(d, poses_cam2world)
-    return vol.extract()
+    return vol
+
+
+def fuse_mesh(depth_u16, poses_cam2world, intrinsic, voxel_length=3.0 / 512, sdf_trunc=0.04, depth_scale=1000.0,
+              depth_trunc=6.0, lattice_offset=0.5, device="cuda"):
+    """One fragment as a mesh: the arguments of fuse_fragment -> (vertices float64 [n,3], triangles int32 [m,3])."""
+    return fuse_volume(depth_u16, poses_cam2world, intrinsic, voxel_length, sdf_trunc, depth_scale, depth_trunc,
+                       lattice_offset, device).extract_mesh()
+
+
+def fuse_fragment(depth_u16, poses_cam2world, intrinsic, voxel_length=3.0 / 512, sdf_trunc=0.04, depth_scale=1000.0,
+                  depth_trunc=6.0, lattice_offset=0.5, device="cuda"):
+    """One fragment: depth_u16 [F,H,W] uint16, poses_cam2world [F,4,4], intrinsic [3,3] -> float64 [n,3]."""
+    return fuse_volume(depth_u16, poses_cam2world, intrinsic, voxel_length, sdf_trunc, depth_scale, depth_trunc,
+                       lattice_offset, device).extract()

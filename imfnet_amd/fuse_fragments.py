@@ -4,7 +4,7 @@ volume on the GPU (imfnet_amd/fuse.py, csrc/tsdf.hip).
     python -m imfnet_amd.fuse_fragments --dataset_root <raw> --out_root <fragments>
 
     <raw>/<scene>/camera-intrinsics.txt, <raw>/<scene>/<seq>/*.color.jpg + .depth.png + .pose.txt
- -> <out>/<scene>/<seq>/cloud_bin_K.ply, cloud_bin_K.pose.npy, cloud_bin_K.frames.pkl
+ -> <out>/<scene>/<seq>/cloud_bin_K.ply, cloud_bin_K.pose.npy, cloud_bin_K.frames.pkl (--mesh: cloud_bin_K.mesh.ply too)
 
 Kept from upstream: sequences and colour files in alphanumeric order; fragments of --frames_per_frag frames; poses read
 as float32 and made relative to the fragment's first frame; a frame whose pose holds a NaN is skipped; a fragment whose
@@ -15,6 +15,8 @@ colour file to cloud_bin_K_0.jpg, the name generate_desc and the trainer look fo
 its data set used is not recorded).  The PLY holds float x, y, z only, no colours; --normals adds float nx, ny, nz as
 upstream's fragments carry them (estimate_normals after the extract: knn 30, within 5 voxel lengths, facing the
 fragment's first camera, the origin; upstream signs them by the TSDF gradient and sums the covariance as cumulants).
+--mesh also writes the surface of the same volume as triangles (TSDFVolume.extract_mesh) to
+cloud_bin_K.mesh.ply; cloud_bin_K.ply keeps its bytes.
 --threads sizes the decode pool (upstream: joblib workers); the next fragment is decoded while the GPU works on the
 current one.
 """
@@ -141,6 +143,24 @@ def write_ply_normals(path, xyz, normals):
     os.replace(path + ".tmp", path)
 
 
+def write_ply_mesh(path, vertices, triangles):
+    """A triangle mesh in write_ply's layout (binary little-endian, float x, y, z) followed by `element face` with
+    `property list uchar int vertex_indices`; the file appears under its name only when it is complete."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3).astype("<f4")
+    t = np.asarray(triangles).reshape(-1, 3)
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError(f"{path}: triangle indices outside [0, {len(v)})")
+    faces = np.empty(len(t), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    faces["n"], faces["v"] = 3, t
+    head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\n"
+            f"property float z\nelement face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path + ".tmp", "wb") as fh:
+        fh.write(head.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(faces.tobytes())
+    os.replace(path + ".tmp", path)
+
+
 def fragment_normals(cfg, xyz):
     from .matching import estimate_normals
     if len(xyz) == 0:
@@ -148,7 +168,9 @@ def fragment_normals(cfg, xyz):
     return estimate_normals(xyz, knn=30, max_radius=5.0 * cfg.voxel_length, viewpoint=np.zeros(3), device=cfg.device)[0]
 
 
-def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None):
+def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None, mesh=None):
+    if mesh is not None:
+        write_ply_mesh(os.path.join(out_folder, f"cloud_bin_{frag_id}.mesh.ply"), *mesh)
     if normals is None:
         write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz)
     else:
@@ -161,15 +183,17 @@ def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None):
 
 
 def gpu_fuse(cfg, intrinsic, frag):
-    from .fuse import fuse_fragment
-    return fuse_fragment(frag["depth"], frag["poses"], intrinsic, voxel_length=cfg.voxel_length, sdf_trunc=SDF_TRUNC,
-                         depth_scale=cfg.depth_scale, depth_trunc=cfg.depth_trunc, lattice_offset=cfg.lattice_offset,
-                         device=cfg.device)
+    """The fragment's points; under --mesh (points, (vertices, triangles)) of the same volume."""
+    from .fuse import fuse_volume
+    vol = fuse_volume(frag["depth"], frag["poses"], intrinsic, voxel_length=cfg.voxel_length, sdf_trunc=SDF_TRUNC,
+                      depth_scale=cfg.depth_scale, depth_trunc=cfg.depth_trunc, lattice_offset=cfg.lattice_offset,
+                      device=cfg.device)
+    return (vol.extract(), vol.extract_mesh()) if getattr(cfg, "mesh", False) else vol.extract()
 
 
 def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
-    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` does the volume work, `normals(cfg, xyz)` the
-    normals under --normals.  Returns the fragments written."""
+    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` (under --mesh: `(points, (vertices, triangles))`)
+    does the volume work, `normals(cfg, xyz)` the normals under --normals.  Returns the fragments written."""
     if cfg.voxel_length is None:
         cfg.voxel_length = cfg.tsdf_cubic_size / 512.0
     ensure_dir(cfg.out_root)
@@ -194,10 +218,12 @@ def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
                 log(f"    {scene}/{seq} fragment {k}: no pose for its first frame, nothing written")
                 continue
             xyz = fuse(cfg, intrinsic, frag)
+            xyz, mesh = xyz if isinstance(xyz, tuple) else (xyz, None)
             nrm = normals(cfg, xyz) if cfg.normals else None
-            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz, nrm)
+            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz, nrm, mesh)
             written += 1
-            log(f"    {scene}/{seq}/cloud_bin_{k}: {len(frag['stems'])} frames, {len(xyz)} points")
+            log(f"    {scene}/{seq}/cloud_bin_{k}: {len(frag['stems'])} frames, {len(xyz)} points"
+                + (f", {len(mesh[1])} triangles" if mesh is not None else ""))
     return written
 
 
@@ -218,6 +244,8 @@ def parse_args(argv=None):
     ap.add_argument("--write_image", action="store_true", help="copy the first integrated frame's colour file to cloud_bin_K_0.jpg")
     ap.add_argument("--normals", action="store_true",
                     help="add float nx, ny, nz to the PLY: k-NN PCA normals (knn 30, 5 voxel lengths) facing the first camera")
+    ap.add_argument("--mesh", action="store_true",
+                    help="also write cloud_bin_K.mesh.ply: the triangle mesh of the same volume (marching tetrahedra)")
     ap.add_argument("--device", default="cuda")
     return ap.parse_args(argv)
 

@@ -40,7 +40,8 @@ def list_fragments(source_path):
         if "evaluation" in scene:
             continue
         for fi in get_file_list(os.path.join(scene, "seq-01"), ".ply"):
-            frags.append((scene, fi))
+            if not fi.endswith(".mesh.ply"):                 # fuse_fragments --mesh: a surface, not a fragment
+                frags.append((scene, fi))
     return frags
 
 

@@ -1037,6 +1037,18 @@ size_t imf_tsdf_extract_workspace_bytes(int64_t max_units);
 int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
                      const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out,
                      int64_t capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
+/* The triangle mesh of the volume: marching tetrahedra on the Kuhn split of every cell whose eight samples are valid
+ * (w != 0 and tsdf < 0.98; inside = tsdf < 0); the rule stands at the head of csrc/tsdf_mesh.hip.  out_vertices fp64 [n,3]
+ * in the order (unit, voxel, edge slot), out_triangles int32 [m,3] in the order (unit, cell, tetrahedron, triangle),
+ * counter-clockwise seen from the free-space side.  out_n: device int64[2] = {vertices, triangles}, always written; when
+ * either exceeds its capacity, or the vertices exceed 2^31 - 1 (the indices are int32), nothing is written to the
+ * outputs (both capacities 0: count only, the outputs may be NULL).  No host synchronisation, integer atomics only and
+ * none of them decides an output position: two calls give the same bytes. */
+size_t imf_tsdf_mesh_workspace_bytes(int64_t max_units);
+int imf_tsdf_mesh(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
+                  const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out_vertices,
+                  int64_t vertex_capacity, int32_t *out_triangles, int64_t triangle_capacity, int64_t *out_n,
+                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- Fragment overlap: the 3DMatch training-pair builder (imfnet_amd/overlap.py, imfnet_amd.compute_overlap) ------------
  * Replace the pyflann nearest-neighbour queries of data/compute_overlap.py:93-141 (the loop restated in csrc/overlap.hip):

@@ -2,6 +2,8 @@
 (tests/tsdf_scene.py), next to the NumPy restatement (tests/tsdf_restate.py) on the same input.
 
   allocate / integrate / extract   each call between device synchronisations, inputs resident (medians)
+  mesh                              TSDFVolume.extract_mesh on the same volume: the count call, the sized call, the download
+  mesh_device                       the sized imf_tsdf_mesh call alone, buffers resident (cells, count, two scans, two writes)
   fragment                          fuse_fragment host to host: upload of the depth frames, the three calls, the download
   restatement                       the NumPy restatement, its units split over at most 16 threads (one run)
   integrate_bytes_per_s             units x 4096 voxels x 8 B read and written once, over the integrate time
@@ -34,6 +36,24 @@ def median_ms(fn, iters, warmup):
         torch.cuda.synchronize()
         out.append((time.perf_counter() - t) * 1e3)
     return float(np.median(out))
+
+
+def mesh_device_call(vol, n_vertices, n_triangles):
+    """One sized imf_tsdf_mesh call on resident buffers, as a function to time."""
+    import ctypes as C
+    L, dev = vol.L, vol.device
+    p = lambda t: C.c_void_p(t.data_ptr())
+    ws = torch.empty(L.imf_tsdf_mesh_workspace_bytes(vol.n_units), dtype=torch.uint8, device=dev)
+    out_n = torch.zeros(2, dtype=torch.int64, device=dev)
+    v = torch.empty((max(1, n_vertices), 3), dtype=torch.float64, device=dev)
+    t = torch.empty((max(1, n_triangles), 3), dtype=torch.int32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def call():
+        rc = L.imf_tsdf_mesh(p(vol._voxels), p(vol._units), p(vol._meta), vol.n_units, p(vol._table), vol.table_capacity,
+                             C.byref(vol.params), p(v), len(v), p(t), len(t), p(out_n), p(ws), ws.numel(), stream)
+        assert rc == 0
+    return call
 
 
 def restate_threaded(R, seq, threads):
@@ -81,6 +101,11 @@ def main():
     res["extract_ms"] = median_ms(lambda: state["vol"].extract(), a.iters, a.warmup)
     pts = state["vol"].extract()
     res["units"], res["points"] = state["vol"].n_units, int(len(pts))
+    res["mesh_ms"] = median_ms(lambda: state["vol"].extract_mesh(), a.iters, a.warmup)
+    verts, tris = state["vol"].extract_mesh()
+    res["mesh_vertices"], res["mesh_triangles"] = int(len(verts)), int(len(tris))
+    res["mesh_device_ms"] = median_ms(mesh_device_call(state["vol"], len(verts), len(tris)), a.iters, a.warmup)
+    res["mesh_over_extract"] = res["mesh_ms"] / res["extract_ms"]
     res["integrate_state_bytes"] = res["units"] * 4096 * 8 * 2
     res["integrate_bytes_per_s"] = res["integrate_state_bytes"] / (res["integrate_ms"] * 1e-3)
     res["voxel_frame_updates_per_s"] = res["units"] * 4096 * a.frames / (res["integrate_ms"] * 1e-3)
