@@ -307,6 +307,9 @@ SIGNATURES = {
     "imf_tsdf_extract": (_I, [_P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _L, _P, _P, _Z, _P]),
     "imf_tsdf_mesh_workspace_bytes": (_Z, [_L]),
     "imf_tsdf_mesh": (_I, [_P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _L, _P, _L, _P, _P, _Z, _P]),
+    "imf_tsdf_integrate_rgb": (_I, [_P, _P, _I, _P, C.POINTER(TsdfParams), _P, _P, _L, _P, _P, _P]),
+    "imf_tsdf_extract_rgb": (_I, [_P, _P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _P, _L, _P, _P, _Z, _P]),
+    "imf_tsdf_mesh_rgb": (_I, [_P, _P, _P, _P, _L, _P, _L, C.POINTER(TsdfParams), _P, _P, _L, _P, _L, _P, _P, _Z, _P]),
     "imf_overlap_index_bytes": (_Z, [_L]),
     "imf_overlap_index_workspace_bytes": (_Z, [_L]),
     "imf_overlap_index_build": (_I, [_P, _L, _D, _P, _Z, C.POINTER(OverlapIndex), _P, _Z, _P]),

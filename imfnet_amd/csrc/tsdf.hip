@@ -23,9 +23,24 @@
 //     p0 + voxel_length |f0| / (|f0| + |f1|) along the axis.
 // Geometry is fp64, tsdf and weight are float32.  Contraction into fused multiply-adds is switched off for this file
 // so that the arithmetic above is the arithmetic that runs (tests/tsdf_restate.py states it in NumPy).
+// Colour (imf_tsdf_integrate_rgb / imf_tsdf_extract_rgb; upstream's volume is RGB8 and integrates the colour frame with
+// the depth frame), pinned as the depth rule is ([RECALLED] from UniformTSDFVolume; tests/tsdf_color_restate.py in NumPy):
+//   a colour image uint8 [H][W][3] = R, G, B comes beside every depth image.  Exactly when a frame updates a voxel's tsdf
+//   (every skip above has passed), with the same pixel (u, v) and w = the weight BEFORE this frame's increment, per channel:
+//     c[k] = (c[k] * w + (float)rgb[v][u][k]) / (w + 1)          float32 on the 0..255 scale, one __fdiv_rn, no contraction
+//   so a constant colour stays exactly that colour, and frames fed in several calls give the bits of one call.
+//   extract: the point between the samples lo and hi gets, with t = |f_lo| / (|f_lo| + |f_hi|) as its position uses it,
+//     c = c_lo + t * (c_hi - c_lo) per channel in fp64, uint8 = floor(c + 0.5) clamped to [0, 255] (tsdf_shared.h:
+//     edge_color).  Both ends have w != 0, so both have a colour.
+//   Open3D keeps the colour as three doubles per voxel; here three float32, like the tsdf beside them.
+//   The colour state is a buffer of its own, float32 [rows, 3, 4096]: per unit one plane of 4096 per channel, so that a
+//   wavefront's voxels read and write consecutive dwords, and `voxels` keeps its [rows, 4096, 2] for every other consumer.
+//   Colour is a compile-time switch of k_tsdf_integrate and of k_tsdf_extract's write pass: the depth-only instantiations
+//   are the code they were, the coloured ones share every line of the projection and the scans, and leave the same
+//   (tsdf, weight) and the same points bit for bit.
 // Changed against Open3D, on purpose: a frame is integrated into EVERY opened unit it sees, not only into the units its
 // own stride-4 samples opened (one thread owns a voxel and walks the frames; a unit list per frame would add a
-// second indirection for a difference of a few free-space voxels); no colour; no normals.
+// second indirection for a difference of a few free-space voxels); colour as float32; no normals.
 //
 // Device design.  The unit table is the library's open-addressing table of 16-byte imf_slot entries (common.h: the same
 // slot hash and double-hashing step), key = the biased unit coordinate with z in the high field, so that ascending keys
@@ -168,11 +183,15 @@ __device__ __forceinline__ bool frame_misses_unit(const double *M, const TsdfP &
   return false;
 }
 
+// COLOR = true also folds the colour frames into the colour planes, at exactly the updates of the tsdf
+template <bool COLOR>
 __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_integrate(const uint16_t *__restrict__ depth, int F,
                                                                 const double *__restrict__ w2c, TsdfP P,
                                                                 const int32_t *__restrict__ units,
                                                                 const int32_t *__restrict__ n_units,
-                                                                float2 *__restrict__ vox) {
+                                                                float2 *__restrict__ vox,
+                                                                const uint8_t *__restrict__ color,
+                                                                float *__restrict__ col) {
   const int u = blockIdx.x;
   if (u >= n_units[0]) return;
   __shared__ uint32_t act[kTsdfMaxFrames / 32];
@@ -195,6 +214,11 @@ __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_integrate(const uint16_t 
     const double pz = ((double)(kUnitRes * uz + lz) + P.off) * P.vl;
     const int64_t at = (int64_t)u * kUnitVoxels + lz * 256 + t;
     float2 s = vox[at];                                   // x = tsdf, y = weight
+    float c[3] = {0.f, 0.f, 0.f};
+    if constexpr (COLOR) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) c[k] = col[color_index(u, k, lz * 256 + t)];
+    }
     for (int f = 0; f < F; ++f) {
       if (!((act[f >> 5] >> (f & 31)) & 1u)) continue;    // wave-uniform
       const double *M = w2c + 12 * f;
@@ -213,22 +237,34 @@ __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_integrate(const uint16_t 
       if (sdf <= -P.trunc) continue;
       const float nw = (float)fmin(1.0, sdf / P.trunc);
       s.x = __fdiv_rn(s.x * s.y + nw, s.y + 1.0f);
+      if constexpr (COLOR) {                                // the same pixel, the weight before its increment
+        const uint8_t *px = color + (((int64_t)f * P.H + iv) * P.W + iu) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = __fdiv_rn(c[k] * s.y + (float)px[k], s.y + 1.0f);
+      }
       s.y = s.y + 1.0f;
     }
     vox[at] = s;
+    if constexpr (COLOR) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) col[color_index(u, k, lz * 256 + t)] = c[k];
+    }
   }
 }
 
 __device__ __forceinline__ bool tsdf_surface_side(float2 s) { return s.y != 0.0f && s.x < 0.98f && s.x != 0.0f; }
 
 // WRITE = false: unit_cnt[u] = points of unit u.  WRITE = true: the points, at offsets[u] + their place in the unit.
-template <bool WRITE>
+// COLOR (with WRITE): row i of out_rgb = the colour of row i of out.
+template <bool WRITE, bool COLOR>
 __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_extract(const float2 *__restrict__ vox, const int32_t *__restrict__ units,
                                                               const int32_t *__restrict__ n_units, int max_units,
                                                               const imf_slot *__restrict__ tab, uint32_t capmask, TsdfP P,
                                                               int32_t *__restrict__ unit_cnt,
                                                               const int64_t *__restrict__ offsets, int64_t capacity,
-                                                              double *__restrict__ out) {
+                                                              double *__restrict__ out,
+                                                              const float *__restrict__ col,
+                                                              uint8_t *__restrict__ out_rgb) {
   const int u = blockIdx.x, n = min(n_units[0], max_units);
   if (u >= n) return;
   if (WRITE && offsets[n] > capacity) return;
@@ -292,9 +328,15 @@ __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_extract(const float2 *__r
       for (int a = 0; a < 3; ++a) {
         if (!cross[a] || row >= capacity) continue;
         const double r1 = fabs((double)f1[a]);
+        const double tt = r0 / (r0 + r1);
         double p[3] = {p0[0], p0[1], p0[2]};
-        p[a] = p0[a] + P.vl * (r0 / (r0 + r1));
+        p[a] = p0[a] + P.vl * tt;
         out[3 * row + 0] = p[0]; out[3 * row + 1] = p[1]; out[3 * row + 2] = p[2];
+        if constexpr (COLOR) {                              // hi: the sample the crossing was found at (above)
+          const int step_a = a == 0 ? 1 : (a == 1 ? 16 : 256);
+          const bool in_a = a == 0 ? lx < 15 : (a == 1 ? ly < 15 : lz < 15);
+          edge_color(col, u, l, in_a ? u : nb[a], in_a ? l + step_a : l - 15 * step_a, tt, out_rgb + 3 * row);
+        }
         ++row;
       }
     }
@@ -311,6 +353,76 @@ __global__ __launch_bounds__(kTsdfThreads) void k_tsdf_extract(const float2 *__r
 }  // namespace imf
 
 using namespace imf;
+
+// imf_tsdf_integrate and imf_tsdf_integrate_rgb: one set of checks, the kernel with or without the colour planes
+static int tsdf_integrate(const char *what, bool rgb, const uint16_t *depth, const uint8_t *color, int n_frames,
+                          const double *world2cam, const imf_tsdf_params *params, const int32_t *units,
+                          const int32_t *n_units, int64_t max_units, float *voxels, float *colors, void *stream) {
+  TsdfP P;
+  int rc = tsdf_params(what, params, P);
+  if (rc) return rc;
+  IMF_REQUIRE(n_frames >= 0 && n_frames <= kTsdfMaxFrames, "%s: n_frames=%d", what, n_frames);
+  IMF_REQUIRE(max_units >= 0 && max_units <= kTsdfMaxUnits, "%s: max_units=%lld", what, (long long)max_units);
+  if (n_frames == 0 || max_units == 0) return IMF_OK;
+  IMF_REQUIRE(depth && world2cam && units && n_units && voxels, "%s: null pointer", what);
+  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "%s: voxels must be 8-byte aligned", what);
+  float2 *vox = reinterpret_cast<float2 *>(voxels);
+  if (rgb) {
+    IMF_REQUIRE(color, "%s: color is NULL", what);
+    IMF_REQUIRE(colors, "%s: colors is NULL", what);
+    IMF_REQUIRE(((uintptr_t)colors & 3) == 0, "%s: colors must be 4-byte aligned", what);
+    k_tsdf_integrate<true><<<(unsigned)max_units, kTsdfThreads, 0, (hipStream_t)stream>>>(depth, n_frames, world2cam, P, units,
+                                                                                         n_units, vox, color, colors);
+  } else {
+    k_tsdf_integrate<false><<<(unsigned)max_units, kTsdfThreads, 0, (hipStream_t)stream>>>(depth, n_frames, world2cam, P, units,
+                                                                                          n_units, vox, nullptr, nullptr);
+  }
+  IMF_CHECK_LAUNCH(what);
+  return IMF_OK;
+}
+
+// imf_tsdf_extract and imf_tsdf_extract_rgb: the same count pass and scan, the write pass with or without the colours
+static int tsdf_extract(const char *what, bool rgb, const float *voxels, const float *colors, const int32_t *units,
+                        const int32_t *n_units, int64_t max_units, const imf_slot *table, int64_t table_capacity,
+                        const imf_tsdf_params *params, double *out, uint8_t *out_rgb, int64_t capacity, int64_t *out_n,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  TsdfP P;
+  int rc = tsdf_params(what, params, P);
+  if (rc) return rc;
+  IMF_REQUIRE(voxels && units && n_units && table && out_n && workspace, "%s: null pointer", what);
+  IMF_REQUIRE(max_units >= 1 && max_units <= kTsdfMaxUnits, "%s: max_units=%lld", what, (long long)max_units);
+  IMF_REQUIRE(is_pow2(table_capacity) && table_capacity <= (1ll << 31), "%s: table_capacity=%lld", what,
+              (long long)table_capacity);
+  IMF_REQUIRE(capacity >= 0 && (out || capacity == 0), "%s: capacity=%lld with out=%p", what, (long long)capacity,
+              (const void *)out);
+  if (rgb) {
+    IMF_REQUIRE(colors, "%s: colors is NULL", what);
+    IMF_REQUIRE(out_rgb || capacity == 0, "%s: out_rgb is NULL with capacity=%lld", what, (long long)capacity);
+    IMF_REQUIRE(((uintptr_t)colors & 3) == 0, "%s: colors must be 4-byte aligned", what);
+  }
+  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "%s: voxels must be 8-byte aligned", what);
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", what);
+  IMF_REQUIRE(workspace_bytes >= imf_tsdf_extract_workspace_bytes(max_units), "%s: workspace %zu < %zu", what, workspace_bytes,
+              imf_tsdf_extract_workspace_bytes(max_units));
+  hipStream_t st = (hipStream_t)stream;
+  char *ws = (char *)workspace;
+  int32_t *cnt = (int32_t *)ws;
+  int64_t *offsets = (int64_t *)(ws + align256((size_t)max_units * 4));
+  const uint32_t capmask = (uint32_t)(table_capacity - 1);
+  const float2 *vox = reinterpret_cast<const float2 *>(voxels);
+  const unsigned grid = (unsigned)max_units;
+  k_tsdf_extract<false, false><<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, cnt,
+                                                              nullptr, 0, nullptr, nullptr, nullptr);
+  k_tsdf_scan<<<1, 1024, 0, st>>>(cnt, n_units, (int)max_units, offsets, out_n);
+  if (capacity > 0 && rgb)
+    k_tsdf_extract<true, true><<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, nullptr,
+                                                              offsets, capacity, out, colors, out_rgb);
+  else if (capacity > 0)
+    k_tsdf_extract<true, false><<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, nullptr,
+                                                               offsets, capacity, out, nullptr, nullptr);
+  IMF_CHECK_LAUNCH(what);
+  return IMF_OK;
+}
 
 extern "C" {
 
@@ -362,18 +474,15 @@ int imf_tsdf_allocate(const uint16_t *depth, int n_frames, const double *cam2wor
 
 int imf_tsdf_integrate(const uint16_t *depth, int n_frames, const double *world2cam, const imf_tsdf_params *params,
                        const int32_t *units, const int32_t *n_units, int64_t max_units, float *voxels, void *stream) {
-  TsdfP P;
-  int rc = tsdf_params("imf_tsdf_integrate", params, P);
-  if (rc) return rc;
-  IMF_REQUIRE(n_frames >= 0 && n_frames <= kTsdfMaxFrames, "imf_tsdf_integrate: n_frames=%d", n_frames);
-  IMF_REQUIRE(max_units >= 0 && max_units <= kTsdfMaxUnits, "imf_tsdf_integrate: max_units=%lld", (long long)max_units);
-  if (n_frames == 0 || max_units == 0) return IMF_OK;
-  IMF_REQUIRE(depth && world2cam && units && n_units && voxels, "imf_tsdf_integrate: null pointer");
-  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "imf_tsdf_integrate: voxels must be 8-byte aligned");
-  k_tsdf_integrate<<<(unsigned)max_units, kTsdfThreads, 0, (hipStream_t)stream>>>(depth, n_frames, world2cam, P, units, n_units,
-                                                                                 reinterpret_cast<float2 *>(voxels));
-  IMF_CHECK_LAUNCH("imf_tsdf_integrate");
-  return IMF_OK;
+  return tsdf_integrate("imf_tsdf_integrate", false, depth, nullptr, n_frames, world2cam, params, units, n_units, max_units,
+                        voxels, nullptr, stream);
+}
+
+int imf_tsdf_integrate_rgb(const uint16_t *depth, const uint8_t *color, int n_frames, const double *world2cam,
+                           const imf_tsdf_params *params, const int32_t *units, const int32_t *n_units, int64_t max_units,
+                           float *voxels, float *colors, void *stream) {
+  return tsdf_integrate("imf_tsdf_integrate_rgb", true, depth, color, n_frames, world2cam, params, units, n_units, max_units,
+                        voxels, colors, stream);
 }
 
 size_t imf_tsdf_extract_workspace_bytes(int64_t max_units) {
@@ -384,33 +493,16 @@ size_t imf_tsdf_extract_workspace_bytes(int64_t max_units) {
 int imf_tsdf_extract(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
                      const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out,
                      int64_t capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream) {
-  TsdfP P;
-  int rc = tsdf_params("imf_tsdf_extract", params, P);
-  if (rc) return rc;
-  IMF_REQUIRE(voxels && units && n_units && table && out_n && workspace, "imf_tsdf_extract: null pointer");
-  IMF_REQUIRE(max_units >= 1 && max_units <= kTsdfMaxUnits, "imf_tsdf_extract: max_units=%lld", (long long)max_units);
-  IMF_REQUIRE(is_pow2(table_capacity) && table_capacity <= (1ll << 31), "imf_tsdf_extract: table_capacity=%lld",
-              (long long)table_capacity);
-  IMF_REQUIRE(capacity >= 0 && (out || capacity == 0), "imf_tsdf_extract: capacity=%lld with out=%p", (long long)capacity,
-              (const void *)out);
-  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "imf_tsdf_extract: voxels must be 8-byte aligned");
-  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_tsdf_extract: workspace must be 256-byte aligned");
-  IMF_REQUIRE(workspace_bytes >= imf_tsdf_extract_workspace_bytes(max_units), "imf_tsdf_extract: workspace %zu < %zu",
-              workspace_bytes, imf_tsdf_extract_workspace_bytes(max_units));
-  hipStream_t st = (hipStream_t)stream;
-  char *ws = (char *)workspace;
-  int32_t *cnt = (int32_t *)ws;
-  int64_t *offsets = (int64_t *)(ws + align256((size_t)max_units * 4));
-  const uint32_t capmask = (uint32_t)(table_capacity - 1);
-  const float2 *vox = reinterpret_cast<const float2 *>(voxels);
-  k_tsdf_extract<false><<<(unsigned)max_units, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, cnt,
-                                                                     nullptr, 0, nullptr);
-  k_tsdf_scan<<<1, 1024, 0, st>>>(cnt, n_units, (int)max_units, offsets, out_n);
-  if (capacity > 0)
-    k_tsdf_extract<true><<<(unsigned)max_units, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P,
-                                                                      nullptr, offsets, capacity, out);
-  IMF_CHECK_LAUNCH("imf_tsdf_extract");
-  return IMF_OK;
+  return tsdf_extract("imf_tsdf_extract", false, voxels, nullptr, units, n_units, max_units, table, table_capacity, params, out,
+                      nullptr, capacity, out_n, workspace, workspace_bytes, stream);
+}
+
+int imf_tsdf_extract_rgb(const float *voxels, const float *colors, const int32_t *units, const int32_t *n_units,
+                         int64_t max_units, const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params,
+                         double *out, uint8_t *out_rgb, int64_t capacity, int64_t *out_n, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  return tsdf_extract("imf_tsdf_extract_rgb", true, voxels, colors, units, n_units, max_units, table, table_capacity, params,
+                      out, out_rgb, capacity, out_n, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

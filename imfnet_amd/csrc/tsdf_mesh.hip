@@ -26,6 +26,11 @@
 //     of an even permutation, an odd one (tetrahedra 1, 2, 5) swaps.  Positions are never consulted, so a vertex that
 //     lands on a corner (f = 0) gives a zero-area triangle that is still wound consistently.
 //   order: vertices (unit, voxel (z 16 + y) 16 + x, slot); triangles (unit, cell, tetrahedron, triangle); int32 indices.
+//   colour (imf_tsdf_mesh_rgb; the state and its rule at the head of tsdf.hip): a vertex gets c_lo + t (c_hi - c_lo) per
+//     channel in fp64 with the t above, uint8 = floor(c + 0.5) clamped (tsdf_shared.h: edge_color, the function extract
+//     uses): on slots 0..2 with both ends non-zero the vertex colour is extract's point colour bit for bit.  Both ends of
+//     a vertex's edge are valid, so both have a colour.  Colour is a compile-time switch of k_mesh_vertices alone; the
+//     vertices and triangles of the coloured call are the plain call's.
 //
 // Device design.  Workspace: 1 byte (the 7-bit vertex mask) + 4 bytes (the index of its first vertex) per voxel, and
 // two counts and two offsets per unit.
@@ -219,13 +224,17 @@ __device__ __forceinline__ bool mesh_refused(const int64_t *v_off, const int64_t
   return v_off[n] > v_cap || t_off[n] > t_cap || v_off[n] > 0x7FFFFFFFll;
 }
 
+// COLOR: row i of out_rgb = the colour of vertex row i
+template <bool COLOR>
 __global__ __launch_bounds__(kTsdfThreads) void k_mesh_vertices(const float2 *__restrict__ vox, const int32_t *__restrict__ units,
                                                                const int32_t *__restrict__ n_units, int max_units,
                                                                const imf_slot *__restrict__ tab, uint32_t capmask, TsdfP P,
                                                                const uint8_t *__restrict__ mask,
                                                                const int64_t *__restrict__ v_off,
                                                                const int64_t *__restrict__ t_off, int64_t v_cap, int64_t t_cap,
-                                                               int32_t *__restrict__ v_base, double *__restrict__ out) {
+                                                               int32_t *__restrict__ v_base, double *__restrict__ out,
+                                                               const float *__restrict__ col,
+                                                               uint8_t *__restrict__ out_rgb) {
   const int u = blockIdx.x, n = min(n_units[0], max_units);
   if (u >= n) return;
   if (mesh_refused(v_off, t_off, n, v_cap, t_cap)) return;
@@ -256,10 +265,12 @@ __global__ __launch_bounds__(kTsdfThreads) void k_mesh_vertices(const float2 *__
       const int x = lx + (d & 1), y = ly + ((d >> 1) & 1), z = lz + (d >> 2);
       const int r = nb[halo_unit(x, y, z)];
       const double r1 = r >= 0 ? fabs((double)vox[(int64_t)r * kUnitVoxels + halo_voxel(x, y, z)].x) : 0.0;   // r >= 0 always
-      const double step = P.vl * (r0 / (r0 + r1));
+      const double tt = r0 / (r0 + r1);
+      const double step = P.vl * tt;
       out[3 * row + 0] = (d & 1) ? p0[0] + step : p0[0];
       out[3 * row + 1] = (d & 2) ? p0[1] + step : p0[1];
       out[3 * row + 2] = (d & 4) ? p0[2] + step : p0[2];
+      if constexpr (COLOR) edge_color(col, u, lz * 256 + t, r >= 0 ? r : u, halo_voxel(x, y, z), tt, out_rgb + 3 * row);
       ++row;
     }
   }
@@ -327,32 +338,32 @@ __global__ __launch_bounds__(kTsdfThreads) void k_mesh_triangles(const float2 *_
 
 using namespace imf;
 
-extern "C" {
-
-size_t imf_tsdf_mesh_workspace_bytes(int64_t max_units) {
-  if (max_units < 1 || max_units > kTsdfMaxUnits) return 0;
-  return 2 * align256((size_t)max_units * 4) + 2 * align256((size_t)(max_units + 1) * 8) +
-         align256((size_t)max_units * kUnitVoxels) + align256((size_t)max_units * kUnitVoxels * 4);
-}
-
-int imf_tsdf_mesh(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
-                  const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out_vertices,
-                  int64_t vertex_capacity, int32_t *out_triangles, int64_t triangle_capacity, int64_t *out_n,
-                  void *workspace, size_t workspace_bytes, void *stream) {
+// imf_tsdf_mesh and imf_tsdf_mesh_rgb: the same passes, the vertex pass with or without the colours
+static int tsdf_mesh(const char *what, bool rgb, const float *voxels, const float *colors, const int32_t *units,
+                     const int32_t *n_units, int64_t max_units, const imf_slot *table, int64_t table_capacity,
+                     const imf_tsdf_params *params, double *out_vertices, uint8_t *out_rgb, int64_t vertex_capacity,
+                     int32_t *out_triangles, int64_t triangle_capacity, int64_t *out_n, void *workspace,
+                     size_t workspace_bytes, void *stream) {
   TsdfP P;
-  int rc = tsdf_params("imf_tsdf_mesh", params, P);
+  int rc = tsdf_params(what, params, P);
   if (rc) return rc;
-  IMF_REQUIRE(voxels && units && n_units && table && out_n && workspace, "imf_tsdf_mesh: null pointer");
-  IMF_REQUIRE(max_units >= 1 && max_units <= kTsdfMaxUnits, "imf_tsdf_mesh: max_units=%lld", (long long)max_units);
-  IMF_REQUIRE(is_pow2(table_capacity) && table_capacity <= (1ll << 31), "imf_tsdf_mesh: table_capacity=%lld",
+  IMF_REQUIRE(voxels && units && n_units && table && out_n && workspace, "%s: null pointer", what);
+  IMF_REQUIRE(max_units >= 1 && max_units <= kTsdfMaxUnits, "%s: max_units=%lld", what, (long long)max_units);
+  IMF_REQUIRE(is_pow2(table_capacity) && table_capacity <= (1ll << 31), "%s: table_capacity=%lld", what,
               (long long)table_capacity);
-  IMF_REQUIRE(vertex_capacity >= 0 && (out_vertices || vertex_capacity == 0), "imf_tsdf_mesh: vertex_capacity=%lld with out=%p",
-              (long long)vertex_capacity, (const void *)out_vertices);
+  IMF_REQUIRE(vertex_capacity >= 0 && (out_vertices || vertex_capacity == 0), "%s: vertex_capacity=%lld with out=%p",
+              what, (long long)vertex_capacity, (const void *)out_vertices);
   IMF_REQUIRE(triangle_capacity >= 0 && (out_triangles || triangle_capacity == 0),
-              "imf_tsdf_mesh: triangle_capacity=%lld with out=%p", (long long)triangle_capacity, (const void *)out_triangles);
-  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "imf_tsdf_mesh: voxels must be 8-byte aligned");
-  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "imf_tsdf_mesh: workspace must be 256-byte aligned");
-  IMF_REQUIRE(workspace_bytes >= imf_tsdf_mesh_workspace_bytes(max_units), "imf_tsdf_mesh: workspace %zu < %zu",
+              "%s: triangle_capacity=%lld with out=%p", what, (long long)triangle_capacity, (const void *)out_triangles);
+  if (rgb) {
+    IMF_REQUIRE(colors, "%s: colors is NULL", what);
+    IMF_REQUIRE(out_rgb || vertex_capacity == 0, "%s: out_rgb is NULL with vertex_capacity=%lld", what,
+                (long long)vertex_capacity);
+    IMF_REQUIRE(((uintptr_t)colors & 3) == 0, "%s: colors must be 4-byte aligned", what);
+  }
+  IMF_REQUIRE(((uintptr_t)voxels & 7) == 0, "%s: voxels must be 8-byte aligned", what);
+  IMF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", what);
+  IMF_REQUIRE(workspace_bytes >= imf_tsdf_mesh_workspace_bytes(max_units), "%s: workspace %zu < %zu", what,
               workspace_bytes, imf_tsdf_mesh_workspace_bytes(max_units));
   hipStream_t st = (hipStream_t)stream;
   char *ws = (char *)workspace;
@@ -377,13 +388,45 @@ int imf_tsdf_mesh(const float *voxels, const int32_t *units, const int32_t *n_un
   k_tsdf_scan<<<1, 1024, 0, st>>>(v_cnt, n_units, (int)max_units, v_off, out_n);
   k_tsdf_scan<<<1, 1024, 0, st>>>(t_cnt, n_units, (int)max_units, t_off, out_n + 1);
   if (vertex_capacity > 0 && triangle_capacity > 0) {
-    k_mesh_vertices<<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, mask, v_off, t_off,
-                                                   vertex_capacity, triangle_capacity, v_base, out_vertices);
+    if (rgb)
+      k_mesh_vertices<true><<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, mask, v_off,
+                                                           t_off, vertex_capacity, triangle_capacity, v_base, out_vertices,
+                                                           colors, out_rgb);
+    else
+      k_mesh_vertices<false><<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, P, mask, v_off,
+                                                            t_off, vertex_capacity, triangle_capacity, v_base, out_vertices,
+                                                            nullptr, nullptr);
     k_mesh_triangles<<<grid, kTsdfThreads, 0, st>>>(vox, units, n_units, (int)max_units, table, capmask, mask, v_base, v_off,
                                                     t_off, vertex_capacity, triangle_capacity, out_triangles);
   }
-  IMF_CHECK_LAUNCH("imf_tsdf_mesh");
+  IMF_CHECK_LAUNCH(what);
   return IMF_OK;
+}
+
+extern "C" {
+
+size_t imf_tsdf_mesh_workspace_bytes(int64_t max_units) {
+  if (max_units < 1 || max_units > kTsdfMaxUnits) return 0;
+  return 2 * align256((size_t)max_units * 4) + 2 * align256((size_t)(max_units + 1) * 8) +
+         align256((size_t)max_units * kUnitVoxels) + align256((size_t)max_units * kUnitVoxels * 4);
+}
+
+int imf_tsdf_mesh(const float *voxels, const int32_t *units, const int32_t *n_units, int64_t max_units,
+                  const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out_vertices,
+                  int64_t vertex_capacity, int32_t *out_triangles, int64_t triangle_capacity, int64_t *out_n,
+                  void *workspace, size_t workspace_bytes, void *stream) {
+  return tsdf_mesh("imf_tsdf_mesh", false, voxels, nullptr, units, n_units, max_units, table, table_capacity, params,
+                   out_vertices, nullptr, vertex_capacity, out_triangles, triangle_capacity, out_n, workspace, workspace_bytes,
+                   stream);
+}
+
+int imf_tsdf_mesh_rgb(const float *voxels, const float *colors, const int32_t *units, const int32_t *n_units,
+                      int64_t max_units, const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params,
+                      double *out_vertices, uint8_t *out_rgb, int64_t vertex_capacity, int32_t *out_triangles,
+                      int64_t triangle_capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream) {
+  return tsdf_mesh("imf_tsdf_mesh_rgb", true, voxels, colors, units, n_units, max_units, table, table_capacity, params,
+                   out_vertices, out_rgb, vertex_capacity, out_triangles, triangle_capacity, out_n, workspace, workspace_bytes,
+                   stream);
 }
 
 }  // extern "C"

@@ -28,6 +28,25 @@ __device__ __forceinline__ uint64_t unit_key(int x, int y, int z) {
          (uint64_t)(uint32_t)(x + kCoordLim);
 }
 
+// Colour state: float32 [rows, 3, 4096], one plane of 4096 per channel and unit, so that the thread-per-voxel walks read
+// and write consecutive dwords per channel.  The index of channel k of a voxel:
+__device__ __forceinline__ int64_t color_index(int64_t row, int k, int voxel) {
+  return (row * 3 + k) * kUnitVoxels + voxel;
+}
+
+// The colour of a surface point between the samples lo and hi (row, voxel), t = |f_lo| / (|f_lo| + |f_hi|) as the position
+// uses it: c = c_lo + t (c_hi - c_lo) in fp64 without contraction, uint8 = floor(c + 0.5) clamped to [0, 255] (a NaN: 0).
+__device__ __forceinline__ void edge_color(const float *__restrict__ col, int64_t row_lo, int vox_lo, int64_t row_hi, int vox_hi,
+                                           double t, uint8_t *__restrict__ out) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double lo = (double)col[color_index(row_lo, k, vox_lo)], hi = (double)col[color_index(row_hi, k, vox_hi)];
+    const double q = floor(lo + t * (hi - lo) + 0.5);
+    out[k] = (uint8_t)(int)(!(q >= 0.0) ? 0.0 : (q > 255.0 ? 255.0 : q));
+  }
+}
+
 // one workgroup: exclusive scan of the per-unit counts in unit order -> offsets[0..n], *out_n = offsets[n]
 __global__ __launch_bounds__(1024) void k_tsdf_scan(const int32_t *__restrict__ cnt, const int32_t *__restrict__ n_units,
                                                     int max_units, int64_t *__restrict__ offsets, int64_t *__restrict__ out_n) {

@@ -120,6 +120,46 @@ def read_ply_mesh(path):
     return np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float64), np.ascontiguousarray(faces["v"], np.int32)
 
 
+def read_ply_colors(path):
+    """Vertex red, green, blue of a binary little-endian PLY as uint8 [N,3] (what fuse_fragments' writers add under --color),
+    or None when the vertex element has no red / green / blue.  Plain NumPy: a host path that nothing hot reads."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, n, props, in_vertex, seen_vertex = None, 0, [], False, False
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok:
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                in_vertex = tok[1] == "vertex"
+                if in_vertex:
+                    n, seen_vertex = int(tok[2]), True
+                elif not seen_vertex:
+                    raise ValueError(f"{path}: element {tok[1]} before the vertex element")
+            elif tok[0] == "property" and in_vertex:
+                if tok[1] == "list":
+                    raise ValueError(f"{path}: list property in vertex element")
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        names = [p[0] for p in props]
+        if not all(c in names for c in ("red", "green", "blue")):
+            return None
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: format {fmt} (read_ply_colors reads binary_little_endian)")
+        if any(t != "u1" for nm, t in props if nm in ("red", "green", "blue")):
+            raise ValueError(f"{path}: red / green / blue are not uchar")
+        dt = np.dtype([(nm, "<" + t) for nm, t in props])
+        a = np.frombuffer(f.read(n * dt.itemsize), dtype=dt, count=n)
+    return np.stack([a["red"], a["green"], a["blue"]], 1).astype(np.uint8)
+
+
 def read_image(path):
     """matplotlib.image.imread semantics (generate_desc.py:92): PNG -> float32 in [0,1] (HWC, alpha
     dropped is NOT done by the reference; fixtures are RGB); any other format -> uint8 0..255, which the

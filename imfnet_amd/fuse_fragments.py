@@ -12,13 +12,16 @@ first frame has no pose writes nothing; voxel length --tsdf_cubic_size / 512 and
 The project's own: --voxel_length and --lattice_offset (0.5 = upstream's voxel centres; 0 with --voxel_length 0.006
 gives the lattice of the published 3DMatch fragments); --write_image copies the first integrated frame's
 colour file to cloud_bin_K_0.jpg, the name generate_desc and the trainer look for (upstream writes no image; which frame
-its data set used is not recorded).  The PLY holds float x, y, z only, no colours; --normals adds float nx, ny, nz as
+its data set used is not recorded).  The PLY holds float x, y, z only; --color integrates every frame's .color.jpg with its
+depth (upstream's RGB8 volume; the rule at the head of csrc/tsdf.hip) and adds uchar red, green, blue after the float
+properties, in Open3D's order x y z [nx ny nz] red green blue; --normals adds float nx, ny, nz as
 upstream's fragments carry them (estimate_normals after the extract: knn 30, within 5 voxel lengths, facing the
 fragment's first camera, the origin; upstream signs them by the TSDF gradient and sums the covariance as cumulants).
 --mesh also writes the surface of the same volume as triangles (TSDFVolume.extract_mesh) to
-cloud_bin_K.mesh.ply; cloud_bin_K.ply keeps its bytes.
---threads sizes the decode pool (upstream: joblib workers); the next fragment is decoded while the GPU works on the
-current one.
+cloud_bin_K.mesh.ply (with --color: with vertex colours); cloud_bin_K.ply keeps its bytes.
+--threads sizes the decode pool (upstream: joblib workers); the next fragment's depth (and, under --color, colour) files
+are decoded while the GPU works on the current one.  Without --color every file has the bytes it had before the flag
+existed.
 """
 import argparse
 import concurrent.futures as cf
@@ -89,6 +92,26 @@ def read_depth_png(path, height, width):
     return out
 
 
+def read_color_jpg(path, height, width):
+    """uint8 [height, width, 3] = R, G, B (imf_jpeg_read_u8, bit-identical to PIL on baseline files; PIL for the kinds of
+    JPEG the native reader leaves out)."""
+    L = _lib.lib()
+    out = np.empty((height, width, 3), np.uint8)
+    h, w, c = C.c_int(), C.c_int(), C.c_int()
+    rc = L.imf_jpeg_read_u8(os.fsencode(path), out.ctypes.data_as(C.c_void_p), out.size, C.byref(h), C.byref(w), C.byref(c))
+    if rc == -3:                                             # IMF_EUNSUPPORTED
+        from PIL import Image
+        with Image.open(path) as im:
+            a = np.asarray(im.convert("RGB"))
+        if a.shape != (height, width, 3):
+            raise ValueError(f"{path}: {a.shape[0]} x {a.shape[1]}, expected {height} x {width} (--height / --width)")
+        return np.ascontiguousarray(a, np.uint8)
+    _lib.check(rc, f"imf_jpeg_read_u8({path})")
+    if (h.value, w.value) != (height, width):
+        raise ValueError(f"{path}: {h.value} x {w.value}, expected {height} x {width} (--height / --width)")
+    return out
+
+
 def fragment_ranges(n_frames, frames_per_frag):
     """[(frag_id, first frame, one past the last)]."""
     n_frags = int(math.ceil(float(n_frames) / frames_per_frag))
@@ -115,45 +138,87 @@ def select_frames(color_paths, sid, eid, read_pose=read_extrinsic):
 
 
 def load_fragment(cfg, color_paths, sid, eid, pool):
-    """Poses and decoded depth of one fragment, or None when it writes nothing."""
+    """Poses and decoded depth of one fragment (under --color: `color` uint8 [F,H,W,3] of the same frames too), or None when
+    it writes nothing."""
     base, frames = select_frames(color_paths, sid, eid)
     if base is None:
         return None
+    want_color = getattr(cfg, "color", False)
+    color = pool.map(lambda fr: read_color_jpg(fr[0] + ".color.jpg", cfg.height, cfg.width), frames) if want_color else None
     depth = list(pool.map(lambda fr: read_depth_png(fr[0] + ".depth.png", cfg.height, cfg.width), frames))
     depth = np.stack(depth) if depth else np.zeros((0, cfg.height, cfg.width), np.uint16)
     poses = np.stack([p for _, p in frames]).astype(np.float64) if frames else np.zeros((0, 4, 4))
-    return dict(base=base, stems=[s for s, _ in frames], depth=depth, poses=poses)
+    frag = dict(base=base, stems=[s for s, _ in frames], depth=depth, poses=poses)
+    if want_color:
+        color = list(color)
+        frag["color"] = np.stack(color) if color else np.zeros((0, cfg.height, cfg.width, 3), np.uint8)
+    return frag
 
 
-def write_ply(path, xyz):
+def _rgb_rows(path, rgb, n):
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.shape != (n, 3):
+        raise ValueError(f"{path}: rgb must be uint8 [{n}, 3], got {rgb.dtype} {rgb.shape}")
+    return rgb
+
+
+def _vertex_records(path, floats, rgb):
+    """float32 [n, k] and uint8 [n, 3] -> the packed vertex records `k floats, uchar red, green, blue`."""
+    rec = np.empty(len(floats), np.dtype([("f", "<f4", (floats.shape[1],)), ("c", "u1", (3,))]))
+    rec["f"], rec["c"] = floats, _rgb_rows(path, rgb, len(floats))
+    return rec
+
+
+RGB_PROPERTIES = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+
+
+def write_ply(path, xyz, rgb=None):
+    """float x, y, z (imf_ply_write_points); with `rgb` (uint8 [n,3]) the same header and floats with uchar red, green,
+    blue after them, the file appearing under its name only when it is complete."""
+    if rgb is not None:
+        body = _vertex_records(path, np.asarray(xyz, np.float64).reshape(-1, 3).astype("<f4"), rgb)
+        head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(body)}\nproperty float x\nproperty float y\n"
+                f"property float z\n{RGB_PROPERTIES}end_header\n")
+        with open(path + ".tmp", "wb") as fh:
+            fh.write(head.encode("ascii"))
+            fh.write(body.tobytes())
+        os.replace(path + ".tmp", path)
+        return
     xyz = np.ascontiguousarray(xyz, np.float64)
     rc = _lib.lib().imf_ply_write_points(os.fsencode(path), xyz.ctypes.data_as(C.c_void_p), len(xyz))
     _lib.check(rc, f"imf_ply_write_points({path})")
 
 
-def write_ply_normals(path, xyz, normals):
-    """write_ply's layout (binary little-endian, float32, the same x, y, z bytes) with `float nx, ny, nz` after them; the
-    file appears under its name only when it is complete."""
+def write_ply_normals(path, xyz, normals, rgb=None):
+    """write_ply's layout (binary little-endian, float32, the same x, y, z bytes) with `float nx, ny, nz` after them and,
+    with `rgb`, uchar red, green, blue after those; the file appears under its name only when it is complete."""
     body = np.concatenate([np.asarray(xyz, np.float64), np.asarray(normals, np.float64)], 1).astype("<f4")
+    if rgb is not None:
+        body = _vertex_records(path, body, rgb)
     head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(body)}\nproperty float x\nproperty float y\n"
-            "property float z\nproperty float nx\nproperty float ny\nproperty float nz\nend_header\n")
+            "property float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+            + (RGB_PROPERTIES if rgb is not None else "") + "end_header\n")
     with open(path + ".tmp", "wb") as fh:
         fh.write(head.encode("ascii"))
         fh.write(body.tobytes())
     os.replace(path + ".tmp", path)
 
 
-def write_ply_mesh(path, vertices, triangles):
-    """A triangle mesh in write_ply's layout (binary little-endian, float x, y, z) followed by `element face` with
-    `property list uchar int vertex_indices`; the file appears under its name only when it is complete."""
+def write_ply_mesh(path, vertices, triangles, rgb=None):
+    """A triangle mesh in write_ply's layout (binary little-endian, float x, y, z; with `rgb` uchar red, green, blue per
+    vertex after them) followed by `element face` with `property list uchar int vertex_indices`; the file appears under
+    its name only when it is complete."""
     v = np.asarray(vertices, np.float64).reshape(-1, 3).astype("<f4")
+    if rgb is not None:
+        v = _vertex_records(path, v, rgb)
     t = np.asarray(triangles).reshape(-1, 3)
     if len(t) and (t.min() < 0 or t.max() >= len(v)):
         raise ValueError(f"{path}: triangle indices outside [0, {len(v)})")
     faces = np.empty(len(t), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
     faces["n"], faces["v"] = 3, t
     head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\n"
-            f"property float z\nelement face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+            f"property float z\n{RGB_PROPERTIES if rgb is not None else ''}element face {len(t)}\n"
+            "property list uchar int vertex_indices\nend_header\n")
     with open(path + ".tmp", "wb") as fh:
         fh.write(head.encode("ascii"))
         fh.write(v.tobytes())
@@ -168,13 +233,14 @@ def fragment_normals(cfg, xyz):
     return estimate_normals(xyz, knn=30, max_radius=5.0 * cfg.voxel_length, viewpoint=np.zeros(3), device=cfg.device)[0]
 
 
-def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None, mesh=None):
+def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None, mesh=None, rgb=None):
+    """`mesh`: (vertices, triangles) or, coloured, (vertices, triangles, rgb); `rgb`: the colours of xyz."""
     if mesh is not None:
         write_ply_mesh(os.path.join(out_folder, f"cloud_bin_{frag_id}.mesh.ply"), *mesh)
     if normals is None:
-        write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz)
+        write_ply(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz, rgb)
     else:
-        write_ply_normals(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz, normals)
+        write_ply_normals(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz, normals, rgb)
     np.save(os.path.join(out_folder, f"cloud_bin_{frag_id}.pose.npy"), frag["base"])
     with open(os.path.join(out_folder, f"cloud_bin_{frag_id}.frames.pkl"), "wb") as fh:
         pickle.dump({"frames": frag["stems"]}, fh, protocol=pickle.HIGHEST_PROTOCOL)
@@ -183,17 +249,23 @@ def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None, mesh=None)
 
 
 def gpu_fuse(cfg, intrinsic, frag):
-    """The fragment's points; under --mesh (points, (vertices, triangles)) of the same volume."""
+    """The fragment's points; under --mesh (points, (vertices, triangles)) of the same volume.  Under --color a dict:
+    points, rgb and, under --mesh, mesh = (vertices, triangles, vertex rgb)."""
     from .fuse import fuse_volume
+    color = frag["color"] if getattr(cfg, "color", False) else None
     vol = fuse_volume(frag["depth"], frag["poses"], intrinsic, voxel_length=cfg.voxel_length, sdf_trunc=SDF_TRUNC,
                       depth_scale=cfg.depth_scale, depth_trunc=cfg.depth_trunc, lattice_offset=cfg.lattice_offset,
-                      device=cfg.device)
+                      device=cfg.device, color=color)
+    if color is not None:
+        points, rgb = vol.extract(colors=True)
+        return dict(points=points, rgb=rgb, mesh=vol.extract_mesh(colors=True) if getattr(cfg, "mesh", False) else None)
     return (vol.extract(), vol.extract_mesh()) if getattr(cfg, "mesh", False) else vol.extract()
 
 
 def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
-    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` (under --mesh: `(points, (vertices, triangles))`)
-    does the volume work, `normals(cfg, xyz)` the normals under --normals.  Returns the fragments written."""
+    """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` (under --mesh: `(points, (vertices, triangles))`;
+    under --color: dict(points, rgb, mesh = (vertices, triangles, rgb) or None)) does the volume work, `normals(cfg, xyz)`
+    the normals under --normals.  Returns the fragments written."""
     if cfg.voxel_length is None:
         cfg.voxel_length = cfg.tsdf_cubic_size / 512.0
     ensure_dir(cfg.out_root)
@@ -218,9 +290,13 @@ def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
                 log(f"    {scene}/{seq} fragment {k}: no pose for its first frame, nothing written")
                 continue
             xyz = fuse(cfg, intrinsic, frag)
-            xyz, mesh = xyz if isinstance(xyz, tuple) else (xyz, None)
+            rgb = None
+            if isinstance(xyz, dict):
+                xyz, rgb, mesh = xyz["points"], xyz.get("rgb"), xyz.get("mesh")
+            else:
+                xyz, mesh = xyz if isinstance(xyz, tuple) else (xyz, None)
             nrm = normals(cfg, xyz) if cfg.normals else None
-            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz, nrm, mesh)
+            write_fragment(cfg, os.path.join(cfg.out_root, scene, seq), k, frag, xyz, nrm, mesh, rgb)
             written += 1
             log(f"    {scene}/{seq}/cloud_bin_{k}: {len(frag['stems'])} frames, {len(xyz)} points"
                 + (f", {len(mesh[1])} triangles" if mesh is not None else ""))
@@ -246,6 +322,8 @@ def parse_args(argv=None):
                     help="add float nx, ny, nz to the PLY: k-NN PCA normals (knn 30, 5 voxel lengths) facing the first camera")
     ap.add_argument("--mesh", action="store_true",
                     help="also write cloud_bin_K.mesh.ply: the triangle mesh of the same volume (marching tetrahedra)")
+    ap.add_argument("--color", action="store_true",
+                    help="integrate every frame's .color.jpg too: uchar red, green, blue in the PLY (and, with --mesh, in the mesh)")
     ap.add_argument("--device", default="cuda")
     return ap.parse_args(argv)
 

@@ -1000,7 +1000,8 @@ int imf_robust_transform(const double *pts0, const double *pts1, const double *w
 
 /* ---- Fragment fusion: depth frames -> sparse TSDF volume -> surface points (imfnet_amd/fuse.py) -------------------------
  * Replace Open3D 0.12 ScalableTSDFVolume(voxel_length, sdf_trunc).integrate(...) per frame and extract_point_cloud() as
- * data/fuse_fragments_3DMatch.py:47-96 builds a fragment (the loop restated in csrc/tsdf.hip; no colour, no normals).
+ * data/fuse_fragments_3DMatch.py:47-96 builds a fragment (the loop restated in csrc/tsdf.hip; no normals;
+ * colour: the _rgb calls below).
  * The volume is a set of units of 16^3 voxels: `table` (imf_slot[table_capacity], a power of two >= 2 unit_capacity:
  * imf_hash_capacity(unit_capacity)) maps a unit's integer coordinate to its row, `units` int32 [unit_capacity,3] = (x, y, z)
  * lists the rows in ascending (z, y, x), `voxels` float32 [rows, 4096, 2] = (tsdf, weight) of voxel (z * 16 + y) * 16 + x,
@@ -1049,6 +1050,29 @@ int imf_tsdf_mesh(const float *voxels, const int32_t *units, const int32_t *n_un
                   const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params, double *out_vertices,
                   int64_t vertex_capacity, int32_t *out_triangles, int64_t triangle_capacity, int64_t *out_n,
                   void *workspace, size_t workspace_bytes, void *stream);
+/* Colour (Open3D's RGB8 volumes; the rule stands at the head of csrc/tsdf.hip).  The three calls below are the three calls
+ * above with colour: they leave the same (tsdf, weight) state, points, vertices and triangles, bit for bit, keep the same
+ * count-only contract and make the same refusals; a NULL `color`, `colors` or (with a non-zero capacity) `out_rgb` is
+ * refused with a message that names the argument.
+ * `colors`: the colour state, float32 [rows, 3, 4096] on the 0..255 scale, a buffer of its own beside `voxels` (which
+ * keeps its layout), zeroed by the caller: per unit three planes of 4096, plane k = channel k (R, G, B) of voxel
+ * (z * 16 + y) * 16 + x.  Planes, not [4096, 3] or a padded [4096, 4]: a wavefront's 64 voxels read and write 64 consecutive
+ * dwords per channel, and nothing is padded (12 bytes per voxel).
+ * imf_tsdf_integrate_rgb: `color` uint8 [n_frames, height, width, 3] (R, G, B) beside `depth`; whenever a frame updates a
+ * voxel's tsdf, c[k] = (c[k] * w + color[v][u][k]) / (w + 1) in float32 with the weight before the increment.
+ * imf_tsdf_extract_rgb / imf_tsdf_mesh_rgb: `out_rgb` uint8 [capacity, 3] / [vertex_capacity, 3]; row i is the colour of
+ * row i of out / out_vertices: c_lo + t (c_hi - c_lo) in fp64 with the t of the position, floor(c + 0.5) clamped. */
+int imf_tsdf_integrate_rgb(const uint16_t *depth, const uint8_t *color, int n_frames, const double *world2cam,
+                           const imf_tsdf_params *params, const int32_t *units, const int32_t *n_units, int64_t max_units,
+                           float *voxels, float *colors, void *stream);
+int imf_tsdf_extract_rgb(const float *voxels, const float *colors, const int32_t *units, const int32_t *n_units,
+                         int64_t max_units, const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params,
+                         double *out, uint8_t *out_rgb, int64_t capacity, int64_t *out_n, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int imf_tsdf_mesh_rgb(const float *voxels, const float *colors, const int32_t *units, const int32_t *n_units,
+                      int64_t max_units, const imf_slot *table, int64_t table_capacity, const imf_tsdf_params *params,
+                      double *out_vertices, uint8_t *out_rgb, int64_t vertex_capacity, int32_t *out_triangles,
+                      int64_t triangle_capacity, int64_t *out_n, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- Fragment overlap: the 3DMatch training-pair builder (imfnet_amd/overlap.py, imfnet_amd.compute_overlap) ------------
  * Replace the pyflann nearest-neighbour queries of data/compute_overlap.py:93-141 (the loop restated in csrc/overlap.hip):

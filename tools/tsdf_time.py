@@ -7,8 +7,11 @@
   fragment                          fuse_fragment host to host: upload of the depth frames, the three calls, the download
   restatement                       the NumPy restatement, its units split over at most 16 threads (one run)
   integrate_bytes_per_s             units x 4096 voxels x 8 B read and written once, over the integrate time
+  --color                           the same legs again on a coloured volume of the same input, in the same process
+                                    (tests/tsdf_color_scene.py paints the frames): color_allocate / integrate / extract /
+                                    mesh / fragment _ms, and each as a ratio to the depth-only leg of this run
 
-Usage: python tools/tsdf_time.py [--iters 5] [--warmup 2] [--frames 50] [--no-restatement] [--out FILE.json]
+Usage: python tools/tsdf_time.py [--iters 5] [--warmup 2] [--frames 50] [--no-restatement] [--color] [--out FILE.json]
 Prints one JSON line (milliseconds, medians)."""
 import argparse
 import concurrent.futures as cf
@@ -74,6 +77,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--no-restatement", action="store_true")
+    ap.add_argument("--color", action="store_true", help="also time a coloured volume on the same input")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     import tsdf_restate as R
@@ -110,6 +114,29 @@ def main():
     res["integrate_bytes_per_s"] = res["integrate_state_bytes"] / (res["integrate_ms"] * 1e-3)
     res["voxel_frame_updates_per_s"] = res["units"] * 4096 * a.frames / (res["integrate_ms"] * 1e-3)
     res["fragment_ms"] = median_ms(lambda: fuse_fragment(seq["depth"], seq["poses"], seq["K"]), a.iters, a.warmup)
+    if a.color:
+        import tsdf_color_scene as CS
+        rgb = CS.make_colors(seq)
+        c = torch.from_numpy(rgb).to(dev)
+
+        def color_allocate():
+            state["cvol"] = TSDFVolume(seq["K"], H, W, unit_capacity=1 << 16, color=True)
+            state["cvol"].allocate(d, seq["poses"])
+
+        def color_integrate():
+            state["cvol"]._voxels = state["cvol"]._colors = None
+            state["cvol"].integrate(d, seq["poses"], c)
+
+        res["color_allocate_ms"] = median_ms(color_allocate, a.iters, a.warmup)
+        res["color_integrate_ms"] = median_ms(color_integrate, a.iters, a.warmup)
+        res["color_extract_ms"] = median_ms(lambda: state["cvol"].extract(colors=True), a.iters, a.warmup)
+        res["color_mesh_ms"] = median_ms(lambda: state["cvol"].extract_mesh(colors=True), a.iters, a.warmup)
+        res["color_fragment_ms"] = median_ms(lambda: fuse_fragment(seq["depth"], seq["poses"], seq["K"], color=rgb), a.iters,
+                                             a.warmup)
+        res["color_points_equal"] = bool(np.array_equal(state["cvol"].extract(colors=True)[0], pts))
+        res["color_state_bytes"] = res["units"] * 4096 * 20 * 2
+        for leg in ("allocate", "integrate", "extract", "mesh", "fragment"):
+            res[f"color_{leg}_ratio"] = res[f"color_{leg}_ms"] / res[f"{leg}_ms"]
     if not a.no_restatement:
         threads = min(16, len(os.sched_getaffinity(0)))
         t = time.perf_counter()
