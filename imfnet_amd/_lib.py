@@ -288,6 +288,9 @@ SIGNATURES = {
     "imf_icp_point_to_point": (_I, [_P, _L, _P, _L, _D, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "imf_icp_plane_workspace_bytes": (_Z, [_L, _L]),
     "imf_icp_point_to_plane": (_I, [_P, _L, _P, _P, _L, _D, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "imf_color_gradient": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    "imf_icp_colored_workspace_bytes": (_Z, [_L, _L]),
+    "imf_icp_colored": (_I, [_P, _P, _L, _P, _P, _P, _P, _L, _D, _D, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "imf_normals_workspace_bytes": (_Z, [_L]),
     "imf_estimate_normals": (_I, [_P, _L, _I, _D, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "imf_fpfh_workspace_bytes": (_Z, [_L, _I]),

@@ -66,12 +66,16 @@
 // pattern are the point-to-point ones above; only the update differs:
 //   r_i = (p_i - q_i) . n_i,  J_i = [p_i x n_i, n_i]  (rotation first),  solve (sum J^T J) x = -(sum J^T r),
 //   update = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5]
-// with p the current source point, q its target and n the target's normal.  k_icp_corr<true> writes per block the fp64
+// with p the current source point, q its target and n the target's normal.  k_icp_corr<kEstPlane> writes per block the fp64
 // partial sums count, sum d^2, the 21 upper entries of J^T J (row-major) and the 6 of J^T r; k_icp_fit<true> adds the block
 // rows in the fixed order of the point-to-point fit and solves the 6x6 system by LDL^T without pivoting.
 // The singular rule: when a pivot d_k <= 1e-12 * (the largest diagonal entry of sum J^T J), or is NaN, the update is the
 // identity (as is the update of an empty correspondence set).  A single-plane target (rank 3) and fewer than 6 independent
 // rows end there: the next stage then repeats the statistics and the stop rule ends the loop at iteration 1.
+//
+// Coloured ICP (imf_icp_colored): the joint fit of csrc/colored_icp.hip, whose head states the rule.  It is the third kind
+// of k_icp_corr: the same loop, correspondences, statistics and launches; the 29 sums of the point-to-plane row are those
+// of lambda J_G^T J_G + (1 - lambda) J_I^T J_I and lambda J_G r_G + (1 - lambda) J_I r_I, and k_icp_fit<true> serves unchanged.
 #include "common.h"
 #include "registration.h"
 #include "point_grid.h"
@@ -110,13 +114,24 @@ __global__ __launch_bounds__(256) void k_icp_start(const double *__restrict__ sr
   cur[3 * i + 0] = p.x; cur[3 * i + 1] = p.y; cur[3 * i + 2] = p.z;
 }
 
-// stage k: k = 0 on the initial points, k = i + 1 after the update of iteration i.  kPlane: the point-to-plane sums, with
-// normals [n_dst, 3] in the target's ORIGINAL order (unused otherwise)
-template <bool kPlane>
+enum Estimation { kEstPoint, kEstPlane, kEstColor };
+
+// what the coloured kind reads besides the normals: intensities of the source rows and of the target, the target's colour
+// gradient [n_dst, 3] (target arrays in the ORIGINAL order), and lambda_geometric.  Unused by the other kinds.
+struct ColorTerm {
+  const double *src_intensity, *dst_intensity, *dst_gradient;
+  double lambda;
+};
+
+// stage k: k = 0 on the initial points, k = i + 1 after the update of iteration i.  kEstPlane: the point-to-plane sums, with
+// normals [n_dst, 3] in the target's ORIGINAL order (unused by kEstPoint); kEstColor: the joint sums in the same layout
+template <Estimation kEst>
 __global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, const double *__restrict__ normals,
                                                           double *__restrict__ cur, int64_t n, double r2, int stage,
-                                                          const IcpState *__restrict__ st, double *__restrict__ partial) {
+                                                          const IcpState *__restrict__ st, double *__restrict__ partial,
+                                                          ColorTerm ct) {
   if (st->done) return;
+  constexpr bool kPlane = kEst != kEstPoint;
   constexpr int kSums = kPlane ? kPlaneSums : kIcpSums, kRow = kPlane ? kPlaneRow : kIcpRow;
   __shared__ double lds4[4];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,7 +150,26 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, const double *
       const V3 q = load3(g.xyz, r);
       v[0] = 1.0;
       v[1] = d2;
-      if constexpr (kPlane) {
+      if constexpr (kEst == kEstColor) {
+        const int j = g.idx[r];
+        const V3 nq = load3(normals, j), gq = load3(ct.dst_gradient, j);
+        const V3 c = cross(p, nq);
+        const double res = dot(sub(p, q), nq);
+        const V3 pt{p.x - res * nq.x, p.y - res * nq.y, p.z - res * nq.z};            // p projected onto q's tangent plane
+        const double ri = ct.src_intensity[i] - (ct.dst_intensity[j] + dot(gq, sub(pt, q)));
+        const double ng = dot(nq, gq);
+        const V3 M{ng * nq.x - gq.x, ng * nq.y - gq.y, ng * nq.z - gq.z};              // -g + (n . g) n
+        const V3 cm = cross(p, M);
+        const double J[6] = {c.x, c.y, c.z, nq.x, nq.y, nq.z}, K[6] = {cm.x, cm.y, cm.z, M.x, M.y, M.z};
+        const double wg = ct.lambda, wi = 1.0 - ct.lambda;
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int b = a; b < 6; ++b) v[k++] = wg * (J[a] * J[b]) + wi * (K[a] * K[b]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[23 + a] = wg * (J[a] * res) + wi * (K[a] * ri);
+      } else if constexpr (kPlane) {
         const V3 nq = load3(normals, g.idx[r]);
         const V3 c = cross(p, nq);
         const double res = dot(sub(p, q), nq);
@@ -370,13 +404,21 @@ size_t icp_workspace_bytes(int64_t n_src, int64_t n_dst, int row) {
   return grid_layout(n_dst).total + align256((size_t)n_src * 24) + align256(nb * row * 8) + align256(sizeof(IcpState));
 }
 
-// both ICP entry points: the argument checks, the grid, 2 (max_iteration + 1) launches; normals: point-to-plane only
-template <bool kPlane>
+// the ICP entry points: the argument checks, the grid, 2 (max_iteration + 1) launches; normals: point-to-plane and coloured,
+// ct: coloured only
+template <Estimation kEst>
 int icp_run(const char *name, const double *src, int64_t n_src, const double *dst, const double *normals, int64_t n_dst,
             double max_corr_dist, const double *init_host, int max_iteration, double *out_T, double *out_stats,
-            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
+            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream, ColorTerm ct = ColorTerm{}) {
+  constexpr bool kPlane = kEst != kEstPoint;
   constexpr int kRow = kPlane ? kPlaneRow : kIcpRow;
   IMF_REQUIRE(src && dst && (normals || !kPlane) && out_T && out_stats && out_meta && workspace, "%s: null pointer", name);
+  if constexpr (kEst == kEstColor) {
+    IMF_REQUIRE(ct.src_intensity, "%s: null pointer (src_intensity)", name);
+    IMF_REQUIRE(ct.dst_intensity, "%s: null pointer (dst_intensity)", name);
+    IMF_REQUIRE(ct.dst_gradient, "%s: null pointer (dst_gradient)", name);
+    IMF_REQUIRE(ct.lambda >= 0.0 && ct.lambda <= 1.0, "%s: lambda_geometric=%g, expected 0..1", name, ct.lambda);   // NaN too
+  }
   IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst < (1ll << 30), "%s: n_src=%lld n_dst=%lld", name,
               (long long)n_src, (long long)n_dst);
   IMF_REQUIRE(max_corr_dist > 0.0 && max_corr_dist < 1e6, "%s: max_corr_dist=%g", name, max_corr_dist);
@@ -400,7 +442,7 @@ int icp_run(const char *name, const double *src, int64_t n_src, const double *ds
   k_icp_start<<<(unsigned)nb, 256, 0, st>>>(src, n_src, init, cur, state);
   const double r2 = max_corr_dist * max_corr_dist;
   for (int stage = 0; stage <= max_iteration; ++stage) {
-    k_icp_corr<kPlane><<<(unsigned)nb, kIcpThreads, 0, st>>>(g, normals, cur, n_src, r2, stage, state, partial);
+    k_icp_corr<kEst><<<(unsigned)nb, kIcpThreads, 0, st>>>(g, normals, cur, n_src, r2, stage, state, partial, ct);
     k_icp_fit<kPlane><<<1, kFitThreads, 0, st>>>(partial, nb, n_src, stage, max_iteration, state, out_T, out_stats, out_meta);
   }
   IMF_CHECK_LAUNCH(name);
@@ -420,8 +462,8 @@ size_t imf_icp_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_worksp
 int imf_icp_point_to_point(const double *src, int64_t n_src, const double *dst, int64_t n_dst, double max_corr_dist,
                            const double *init_host, int max_iteration, double *out_T, double *out_stats,
                            int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
-  return icp_run<false>("imf_icp_point_to_point", src, n_src, dst, nullptr, n_dst, max_corr_dist, init_host, max_iteration,
-                        out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
+  return icp_run<kEstPoint>("imf_icp_point_to_point", src, n_src, dst, nullptr, n_dst, max_corr_dist, init_host,
+                            max_iteration, out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
 }
 
 size_t imf_icp_plane_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_workspace_bytes(n_src, n_dst, kPlaneRow); }
@@ -429,8 +471,19 @@ size_t imf_icp_plane_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_
 int imf_icp_point_to_plane(const double *src, int64_t n_src, const double *dst, const double *dst_normals, int64_t n_dst,
                            double max_corr_dist, const double *init_host, int max_iteration, double *out_T,
                            double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
-  return icp_run<true>("imf_icp_point_to_plane", src, n_src, dst, dst_normals, n_dst, max_corr_dist, init_host,
-                       max_iteration, out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
+  return icp_run<kEstPlane>("imf_icp_point_to_plane", src, n_src, dst, dst_normals, n_dst, max_corr_dist, init_host,
+                            max_iteration, out_T, out_stats, out_meta, workspace, workspace_bytes, stream);
+}
+
+size_t imf_icp_colored_workspace_bytes(int64_t n_src, int64_t n_dst) { return icp_workspace_bytes(n_src, n_dst, kPlaneRow); }
+
+int imf_icp_colored(const double *src, const double *src_intensity, int64_t n_src, const double *dst,
+                    const double *dst_normals, const double *dst_intensity, const double *dst_gradient, int64_t n_dst,
+                    double max_corr_dist, double lambda_geometric, const double *init_host, int max_iteration, double *out_T,
+                    double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream) {
+  return icp_run<kEstColor>("imf_icp_colored", src, n_src, dst, dst_normals, n_dst, max_corr_dist, init_host, max_iteration,
+                            out_T, out_stats, out_meta, workspace, workspace_bytes, stream,
+                            ColorTerm{src_intensity, dst_intensity, dst_gradient, lambda_geometric});
 }
 
 size_t imf_radius_count_workspace_bytes(int64_t n_dst) {

@@ -103,15 +103,19 @@ def sparse_tensor_from_points(xyz, voxel_size, device, feats=None, before_sync=N
     return st, inds
 
 
-def voxel_representatives(xyz, voxel_size, device=None):
+def voxel_representatives(xyz, voxel_size, device=None, return_index=False):
     """The xyz_down `extract_features` returns for these points and this voxel size (every voxel's first point, in the
-    voxel order of the level-0 map), without a network: float64 numpy [M, 3]."""
+    voxel order of the level-0 map), without a network: float64 numpy [M, 3].  With return_index=True also the int64 numpy
+    [M] row of `xyz` every representative is, so that a representative's colour is its own point's colour."""
     device = _cuda_device(torch.device('cuda:0') if device is None else device)
     _, inds = sparse_tensor_from_points(xyz, voxel_size, device)
     if torch.is_tensor(xyz) and xyz.is_cuda:
-        return xyz.detach()[inds.long()].cpu().numpy().astype(np.float64)
+        out = xyz.detach()[inds.long()].cpu().numpy().astype(np.float64)
+        return (out, inds.cpu().numpy().astype(np.int64)) if return_index else out
     host = xyz.detach().numpy() if torch.is_tensor(xyz) else np.asarray(xyz)
-    return host[inds.cpu().numpy().astype(np.int64)].astype(np.float64, copy=False)
+    index = inds.cpu().numpy().astype(np.int64)
+    out = host[index].astype(np.float64, copy=False)
+    return (out, index) if return_index else out
 
 
 def _host_inputs(xyz, image):

@@ -205,6 +205,96 @@ def icp_point_to_plane(src, dst, dst_normals, max_corr_dist, init=None, max_iter
     return _icp("icp_point_to_plane", src, dst, dst_normals, max_corr_dist, init, max_iteration, device)
 
 
+def intensity(rgb):
+    """The intensity coloured ICP reads: (r + g + b) / 765 in float64 from uint8 colours [n, 3] -- the integer sum first,
+    then one division -- in [0, 1].  Host only."""
+    c = np.asarray(rgb)
+    if c.dtype != np.uint8 or c.ndim != 2 or c.shape[1] != 3:
+        raise ImfError(f"intensity: colours must be uint8 [n, 3], got {c.dtype} {c.shape}")
+    return c.astype(np.int64).sum(1).astype(np.float64) / 765.0
+
+
+def _scalars(x, n, device, name):
+    t = torch.as_tensor(x).to(device=device, dtype=torch.float64).contiguous()
+    if t.shape != (n,):
+        raise ImfError(f"{name} must be [{n}], got {tuple(t.shape)}")
+    return t
+
+
+def _color_gradient_device(p, nrm, inten, nbr, counts):
+    """imf_color_gradient on device tensors; returns the device float64 [n, 3] tensor."""
+    n, knn = p.shape[0], nbr.shape[1]
+    out = torch.empty((n, 3), dtype=torch.float64, device=p.device)
+    check(_lib.lib().imf_color_gradient(p.data_ptr(), nrm.data_ptr(), inten.data_ptr(), nbr.data_ptr(), counts.data_ptr(),
+                                        n, knn, out.data_ptr(), _stream()), "imf_color_gradient")
+    return out
+
+
+def color_gradient(points, normals, intensity, neighbors, counts, device="cuda"):
+    """The colour gradient of a cloud for coloured ICP (imf_color_gradient; the rule is stated in csrc/colored_icp.hip):
+    per point the least-squares gradient of `intensity` [n] over its neighbour list, pinned into the tangent plane of its
+    normal.  neighbors int32 [n, knn <= 64] and counts int32 [n] are `estimate_normals(..., return_neighbors=True)`'s.
+    Returns float64 numpy [n, 3]; 0 where a list has fewer than 4 entries or the system is singular."""
+    p = _points(points, device, "points")
+    n = p.shape[0]
+    nrm = _points(normals, p.device, "normals")
+    if nrm.shape != p.shape:
+        raise ImfError(f"color_gradient: normals {tuple(nrm.shape)} for points {tuple(p.shape)}")
+    inten = _scalars(intensity, n, p.device, "intensity")
+    nbr = torch.as_tensor(neighbors).to(device=p.device, dtype=torch.int32).contiguous()
+    if nbr.dim() != 2 or nbr.shape[0] != n or not 1 <= nbr.shape[1] <= 64:
+        raise ImfError(f"color_gradient: neighbors must be [{n}, 1..64], got {tuple(nbr.shape)}")
+    cnt = torch.as_tensor(counts).to(device=p.device, dtype=torch.int32).contiguous()
+    if cnt.shape != (n,):
+        raise ImfError(f"color_gradient: counts must be [{n}], got {tuple(cnt.shape)}")
+    return _color_gradient_device(p, nrm, inten, nbr, cnt).cpu().numpy()
+
+
+def icp_colored(src, src_intensity, dst, dst_normals, dst_intensity, max_corr_dist, init=None, max_iteration=30,
+                lambda_geometric=0.968, dst_gradient=None, gradient_knn=30, gradient_radius=None, device="cuda"):
+    """Open3D registration_colored_icp(src, dst, max_corr_dist, init, TransformationEstimationForColoredICP(
+    lambda_geometric), ICPConvergenceCriteria(max_iteration)) on the device (imf_icp_colored; restated in
+    csrc/colored_icp.hip).  src_intensity [n_src] and dst_intensity [n_dst] are `intensity` of the rows' colours;
+    dst_normals [n_dst, 3] are the caller's.  dst_gradient: `color_gradient` of the target, or None = computed here over
+    the lists of `estimate_normals(dst, knn=gradient_knn, max_radius=gradient_radius or 2 max_corr_dist,
+    return_neighbors=True)` (Open3D's hybrid search of twice the distance; that call's normals are discarded).  Returns what the other ICPs return: (T 4x4 numpy
+    source->target, fitness, inlier RMSE over point distances, iterations run, correspondences)."""
+    if dst_normals is None:
+        raise ImfError("icp_colored: dst_normals is required")
+    s = _points(src, device, "src")
+    d = _points(dst, s.device, "dst")
+    nrm = _points(dst_normals, s.device, "dst_normals")
+    if nrm.shape != d.shape:
+        raise ImfError(f"icp_colored: dst_normals {tuple(nrm.shape)} for dst {tuple(d.shape)}")
+    si = _scalars(src_intensity, s.shape[0], s.device, "src_intensity")
+    di = _scalars(dst_intensity, d.shape[0], s.device, "dst_intensity")
+    if dst_gradient is None:
+        _, counts, nbr = estimate_normals(d, knn=int(gradient_knn), max_radius=gradient_radius or 2.0 * max_corr_dist,
+                                          device=s.device, return_neighbors=True)
+        grad = _color_gradient_device(d, nrm, di, torch.as_tensor(nbr).to(s.device).contiguous(),
+                                      torch.as_tensor(counts).to(s.device).contiguous())
+    else:
+        grad = _points(dst_gradient, s.device, "dst_gradient")
+        if grad.shape != d.shape:
+            raise ImfError(f"icp_colored: dst_gradient {tuple(grad.shape)} for dst {tuple(d.shape)}")
+    L = _lib.lib()
+    nbytes = L.imf_icp_colored_workspace_bytes(s.shape[0], d.shape[0])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    T = torch.empty(16, dtype=torch.float64, device=s.device)
+    stats = torch.empty(2, dtype=torch.float64, device=s.device)
+    meta = torch.zeros(3, dtype=torch.int32, device=s.device)
+    init = _host_T(init)
+    check(L.imf_icp_colored(s.data_ptr(), si.data_ptr(), s.shape[0], d.data_ptr(), nrm.data_ptr(), di.data_ptr(),
+                            grad.data_ptr(), d.shape[0], float(max_corr_dist), float(lambda_geometric),
+                            init.ctypes.data_as(C.c_void_p) if init is not None else None, int(max_iteration), T.data_ptr(),
+                            stats.data_ptr(), meta.data_ptr(), ws.data_ptr(), nbytes, _stream()), "imf_icp_colored")
+    iters, n_corr, err = meta.tolist()
+    if err:
+        raise ImfError("icp_colored: a target point is NaN or beyond the grid's range")
+    fitness, rmse = stats.tolist()
+    return T.cpu().numpy().reshape(4, 4), fitness, rmse, iters, n_corr
+
+
 def information_matrix(src, dst, T=None, max_corr_dist=0.0375, device="cuda"):
     """Open3D get_information_matrix_from_point_clouds(src, dst, max_corr_dist, T) on the device (imf_information_matrix;
     the rules are restated in csrc/information.hip): the sum of G^T G over ICP's correspondences of T . src in dst, G =

@@ -2,12 +2,14 @@
 optimise the pose graph with line processes over the loop closures, and write the fragments' poses.
 
     python -m imfnet_amd.reconstruct --fragments DIR [--descriptor fpfh | --descriptor imfnet -m checkpoint.pth]
-                                     [--voxel_size 0.025] [--refine plane] [--min_fitness 0.3] [--pairs all|FILE]
+                                     [--voxel_size 0.025] [--refine plane|color] [--min_fitness 0.3] [--pairs all|FILE]
                                      [--preference_loop_closure 1.0] [--merge_voxel V] --out DIR
 
 The pipeline of Choi, Zhou, Koltun 2015 after the fragments: DIR holds cloud_bin_K.ply, K = 0..N-1 (with --descriptor
 imfnet also cloud_bin_K_0.png|jpg, found as generate_desc finds them).  Every fragment's features are computed once
-(`register.fragment_features`, and the normals point-to-plane ICP needs).  Every pair i < j -- all of them, or the lines
+(`register.fragment_features`, the normals point-to-plane ICP needs and, with --refine color, the intensities and the
+colour gradient coloured ICP needs: every cloud_bin_K.ply must then carry red, green, blue as `fuse_fragments --color`
+writes them).  Every pair i < j -- all of them, or the lines
 `i j` of --pairs FILE -- is registered with source = j onto target = i (`register.register_features`, seeded with --seed +
 the pair's number), and `matching.information_matrix(src = j, dst = i, T)` is taken at 1.5 voxel.  The pair becomes an edge
 when ICP's fitness is at least --min_fitness; the edge is uncertain (it has a line process) unless j = i + 1.
@@ -65,15 +67,17 @@ def read_pairs(spec, n):
 
 
 def reconstruct(points, images=None, model=None, cfg=None, descriptor="fpfh", voxel_size=0.025, refine="plane",
-                min_fitness=0.3, pairs="all", preference_loop_closure=1.0, seed=0, device="cuda"):
-    """points: the fragments' float64 [n, 3] arrays; images: their [1, C, H, W] arrays (descriptor="imfnet").  Returns
+                min_fitness=0.3, pairs="all", preference_loop_closure=1.0, seed=0, device="cuda", colors=None):
+    """points: the fragments' float64 [n, 3] arrays; images: their [1, C, H, W] arrays (descriptor="imfnet"); colors: their
+    uint8 [n, 3] colours (refine="color").  Returns
     dict(poses [N, 4, 4], edges (list of dicts: i, j, T, info, fitness, rmse, n_corr, uncertain, l, kept), rejected (pairs
     below min_fitness), unreached, E, times)."""
     from .matching import estimate_normals, information_matrix
     from .pose_graph import PoseGraph, optimize
-    from .register import fragment_features, register_features
-    dev = torch.device(device)
+    from .register import check_colors, down_intensity, fragment_features, register_features, target_color_terms
     n = len(points)
+    check_colors(refine, [(f"fragment {k}", points[k], colors[k] if colors is not None else None) for k in range(n)])
+    dev = torch.device(device)
     pair_list = read_pairs(pairs, n) if isinstance(pairs, str) else [(int(i), int(j)) for i, j in pairs]
     r = 1.5 * voxel_size
     times = {}
@@ -90,12 +94,19 @@ def reconstruct(points, images=None, model=None, cfg=None, descriptor="fpfh", vo
         down.append(xyz)
         feat.append(F)
     timed("features", t0)
-    if refine == "plane":
+    if refine in ("plane", "color"):
         t0 = time.time()
         targets = {i for i, _ in pair_list}
         normals = [estimate_normals(down[k], knn=30, max_radius=4.0 * voxel_size, viewpoint=np.zeros(3), device=dev)[0]
                    if k in targets else None for k in range(n)]
         timed("normals", t0)
+    inten, color_terms = [None] * n, [None] * n
+    if refine == "color":                                 # every fragment's intensities, every target's gradient: once
+        t0 = time.time()
+        inten = [down_intensity(points[k], colors[k], down[k], voxel_size, dev) for k in range(n)]
+        color_terms = [target_color_terms(down[k], normals[k], inten[k], voxel_size, dev) if k in targets else None
+                       for k in range(n)]
+        timed("gradient", t0)
 
     graph = PoseGraph(n)
     edges, rejected = [], []
@@ -103,7 +114,8 @@ def reconstruct(points, images=None, model=None, cfg=None, descriptor="fpfh", vo
         t0 = time.time()
         res = register_features(points[j], points[i], (down[j], down[i]), (feat[j], feat[i]), voxel_size=voxel_size,
                                 seed=seed + number, refine=refine, device=dev,
-                                target_normals=normals[i] if refine == "plane" else None)
+                                target_normals=normals[i] if refine in ("plane", "color") else None,
+                                source_intensity=inten[j], target_color=color_terms[i])
         timed("register", t0)
         if not (res["fitness"] >= min_fitness and np.isfinite(res["T"]).all()):
             rejected.append(dict(i=i, j=j, fitness=res["fitness"], rmse=res["rmse"]))
@@ -172,8 +184,14 @@ def make_parser():
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
-    from .dataio import read_ply_points
+    from .dataio import read_ply_colors, read_ply_points
     files = list_fragments(args.fragments)
+    colors = None
+    if args.refine == "color":
+        colors = [read_ply_colors(f) for f in files]
+        for f, c in zip(files, colors):
+            if c is None:
+                raise SystemExit(f"--refine color: {f} has no red, green, blue")
     points = [np.array(read_ply_points(f), np.float64) for f in files]
     model = cfg = images = None
     if args.descriptor == "imfnet":
@@ -184,7 +202,8 @@ def main(argv=None):
     pairs = read_pairs(args.pairs, len(files))
     result = reconstruct(points, images, model, cfg, descriptor=args.descriptor, voxel_size=args.voxel_size,
                          refine=args.refine, min_fitness=args.min_fitness, pairs=pairs,
-                         preference_loop_closure=args.preference_loop_closure, seed=args.seed, device=args.device)
+                         preference_loop_closure=args.preference_loop_closure, seed=args.seed, device=args.device,
+                         colors=colors)
     graph = write_outputs(args.out, result, points, args.merge_voxel, args.device)
     E = result["E"]
     print(json.dumps(dict(fragments=len(files), pairs=len(pairs), edges=len(result["edges"]),

@@ -1,16 +1,20 @@
 """Register one pair of fragments end to end: descriptors, keypoints, RANSAC, ICP refinement.
 
     python -m imfnet_amd.register --source A.ply --source_image A.png --target B.ply --target_image B.png
-                                  [-m checkpoint.pth] [--refine plane] [--out T.txt]
+                                  [-m checkpoint.pth] [--refine {none,point,plane}] [--out T.txt]
     python -m imfnet_amd.register --descriptor fpfh --source A.ply --target B.ply
+    python -m imfnet_amd.register --descriptor fpfh --source A.ply --target B.ply --refine color      (coloured fragments)
 
 The stages are the library's own, in the order scripts/evaluation_3dmatch.py and scripts/benchmark_util.py use them:
 `extract_features` on both fragments, the keypoint draw (`num_keypoints` raw points without replacement from
 RandomState(seed), source first) and `select_keypoints`, RANSAC on the nearest-descriptor correspondences (ransac_n = 3,
 1.5 voxel, edge similarity 0.9), then ICP on the voxel representatives at 1.5 voxel: point-to-point, or point-to-plane
-against the target's `estimate_normals(knn=30, max_radius=4 voxel, viewpoint=origin)`.  --skip_global starts the
-refinement from --init (identity when absent); the descriptors are still extracted.  Without -m the network runs on
-the seeded weights of the test oracle: the global stage is then meaningless, the plumbing is the same.
+against the target's `estimate_normals(knn=30, max_radius=4 voxel, viewpoint=origin)`, or coloured ICP (--refine color:
+both files must carry red, green, blue as `fuse_fragments --color` writes them; a representative has its own point's
+colour; those normals, the colour gradient over the 30 nearest representatives within 4 voxel, 30 iterations,
+lambda_geometric 0.968).  --skip_global starts the refinement from --init (identity when absent); the descriptors are
+still extracted.  Without -m the network runs on the seeded weights of the test oracle: the global stage is then
+meaningless, the plumbing is the same.
 --descriptor fpfh needs neither a checkpoint nor the images (they are not read): the descriptors are `compute_fpfh` on the
 voxel representatives (radius 5 voxel, max_nn 64, normals at 2 voxel facing the origin, zero-padded to 64 columns); the
 keypoints, RANSAC and the refinement are the same.
@@ -28,7 +32,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFINE_CHOICES = ("none", "point", "plane")
+REFINE_CHOICES = ("none", "point", "plane", "color")
 DESCRIPTOR_CHOICES = ("imfnet", "fpfh")
 
 
@@ -83,16 +87,53 @@ def fragment_features(model, cfg, points, image, voxel_size=0.025, device="cuda"
     return np.asarray(xyz, np.float64), F
 
 
+def check_colors(refine, named):
+    """refine="color" needs uint8 [n, 3] colours for every fragment: refused here, before any GPU work."""
+    if refine != "color":
+        return
+    for name, pts, rgb in named:
+        if rgb is None:
+            raise ValueError(f"refine='color': {name} has no colours (red, green, blue)")
+        rgb = np.asarray(rgb)
+        if rgb.dtype != np.uint8 or rgb.shape != (len(pts), 3):
+            raise ValueError(f"refine='color': the colours of {name} must be uint8 [{len(pts)}, 3], got {rgb.dtype} "
+                             f"{rgb.shape}")
+
+
+def down_intensity(points, colors, down, voxel_size, device="cuda"):
+    """`matching.intensity` of the voxel representatives `down` of `points`: every representative's own point's colour."""
+    from .extract import voxel_representatives
+    from .matching import intensity
+    xyz, index = voxel_representatives(np.asarray(points, np.float64), voxel_size, torch.device(device), return_index=True)
+    if not np.array_equal(xyz, down):
+        raise ValueError("down_intensity: `down` is not the voxel representatives of `points` at this voxel size")
+    return intensity(np.asarray(colors)[index])
+
+
+def target_color_terms(down, normals, inten, voxel_size, device="cuda"):
+    """What coloured ICP needs of a target besides its normals: dict(intensity [M], gradient [M, 3]), the gradient over
+    the lists of `estimate_normals(knn=30, max_radius=4 voxel)`."""
+    from .matching import color_gradient, estimate_normals
+    _, counts, nbr = estimate_normals(down, knn=30, max_radius=4.0 * voxel_size, device=device, return_neighbors=True)
+    return dict(intensity=inten, gradient=color_gradient(down, normals, inten, nbr, counts, device=device))
+
+
 def register_features(source, target, down, feat, voxel_size=0.025, num_keypoints=5000, ransac_iter=50000, seed=0,
-                      init=None, skip_global=False, refine="plane", device="cuda", times=None, target_normals=None):
+                      init=None, skip_global=False, refine="plane", device="cuda", times=None, target_normals=None,
+                      source_colors=None, target_colors=None, source_intensity=None, target_color=None):
     """The keypoint draw, RANSAC and the refinement on two fragments' features.  source / target: the raw points; down,
     feat: (source's, target's) `fragment_features`.  target_normals: the target's `estimate_normals(knn=30, max_radius=4
-    voxel, viewpoint=origin)` when the caller holds them (refine="plane"), else computed here.  times: a dict that receives
-    the stage times.  Returns dict(T 4x4 numpy source->target, fitness, rmse, iterations, n_corr, times)."""
-    from .matching import (estimate_normals, icp_point_to_plane, icp_point_to_point, nn_search, ransac_registration,
-                           select_keypoints)
+    voxel, viewpoint=origin)` when the caller holds them (refine="plane" or "color"), else computed here.  refine="color":
+    source_colors / target_colors are the raw points' uint8 [n, 3] colours; source_intensity (`down_intensity` of the
+    source) and target_color (`target_color_terms` of the target) replace them when the caller holds those.  times: a dict
+    that receives the stage times.  Returns dict(T 4x4 numpy source->target, fitness, rmse, iterations, n_corr, times)."""
+    from .matching import (estimate_normals, icp_colored, icp_point_to_plane, icp_point_to_point, nn_search,
+                           ransac_registration, select_keypoints)
     if refine not in REFINE_CHOICES:
         raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
+    check_colors(refine, [(name, pts, rgb) for name, pts, rgb, held in
+                           (("the source", source, source_colors, source_intensity),
+                            ("the target", target, target_colors, target_color)) if held is None])
     dev = torch.device(device)
     times = {} if times is None else times
 
@@ -124,6 +165,22 @@ def register_features(source, target, down, feat, voxel_size=0.025, num_keypoint
         timed("normals", t0)
         t0 = time.time()
         T, fitness, rmse, iters, n_corr = icp_point_to_plane(down[0], down[1], normals, r, init=T, device=dev)
+    elif refine == "color":
+        normals = target_normals
+        if normals is None:
+            normals, _ = estimate_normals(down[1], knn=30, max_radius=4.0 * voxel_size, viewpoint=np.zeros(3), device=dev)
+        timed("normals", t0)
+        t0 = time.time()
+        if source_intensity is None:
+            source_intensity = down_intensity(source, source_colors, down[0], voxel_size, dev)
+        if target_color is None:
+            target_color = target_color_terms(down[1], normals, down_intensity(target, target_colors, down[1], voxel_size,
+                                                                                 dev), voxel_size, dev)
+        timed("gradient", t0)
+        t0 = time.time()
+        T, fitness, rmse, iters, n_corr = icp_colored(down[0], source_intensity, down[1], normals, target_color["intensity"],
+                                                      r, init=T, max_iteration=30, lambda_geometric=0.968,
+                                                      dst_gradient=target_color["gradient"], device=dev)
     elif refine == "point":
         T, fitness, rmse, iters, n_corr = icp_point_to_point(down[0], down[1], r, init=T, max_iteration=30, device=dev)
     else:                                                 # the statistics of the unrefined pose: one correspondence stage
@@ -134,14 +191,16 @@ def register_features(source, target, down, feat, voxel_size=0.025, num_keypoint
 
 def register_pair(model, cfg, source, source_image, target, target_image, voxel_size=0.025, num_keypoints=5000,
                   ransac_iter=50000, seed=0, init=None, skip_global=False, refine="plane", device="cuda",
-                  descriptor="imfnet"):
+                  descriptor="imfnet", source_colors=None, target_colors=None):
     """source / target: float64 [n, 3] points; *_image: [1, C, H, W] arrays as generate_desc feeds them.  With
-    descriptor="fpfh" model, cfg and the images are not used (None will do).  Returns dict(T 4x4 numpy source->target,
+    descriptor="fpfh" model, cfg and the images are not used (None will do).  source_colors / target_colors: the points'
+    uint8 [n, 3] colours, required by refine="color".  Returns dict(T 4x4 numpy source->target,
     fitness, rmse, iterations, n_corr, times)."""
     if refine not in REFINE_CHOICES:
         raise ValueError(f"refine must be one of {REFINE_CHOICES}, got {refine!r}")
     if descriptor not in DESCRIPTOR_CHOICES:
         raise ValueError(f"descriptor must be one of {DESCRIPTOR_CHOICES}, got {descriptor!r}")
+    check_colors(refine, (("the source", source, source_colors), ("the target", target, target_colors)))
     dev = torch.device(device)
     times = {}
     t0 = time.time()
@@ -154,7 +213,7 @@ def register_pair(model, cfg, source, source_image, target, target_image, voxel_
     times["features"] = time.time() - t0
     return register_features(source, target, down, feat, voxel_size=voxel_size, num_keypoints=num_keypoints,
                              ransac_iter=ransac_iter, seed=seed, init=init, skip_global=skip_global, refine=refine,
-                             device=dev, times=times)
+                             device=dev, times=times, source_colors=source_colors, target_colors=target_colors)
 
 
 def make_parser():
@@ -182,7 +241,13 @@ def make_parser():
 def main(argv=None):
     ap = make_parser()
     args = ap.parse_args(argv)
-    from .dataio import read_ply_points
+    from .dataio import read_ply_colors, read_ply_points
+    colors = [None, None]
+    if args.refine == "color":
+        for k, path in enumerate((args.source, args.target)):
+            colors[k] = read_ply_colors(path)
+            if colors[k] is None:
+                ap.error(f"--refine color: {path} has no red, green, blue")
     if args.descriptor == "fpfh":
         model = cfg = src_image = dst_image = None
     else:
@@ -194,7 +259,7 @@ def main(argv=None):
     res = register_pair(model, cfg, read_ply_points(args.source), src_image, read_ply_points(args.target), dst_image,
                         voxel_size=args.voxel_size, num_keypoints=args.num_keypoints, ransac_iter=args.ransac_iter,
                         seed=args.seed, init=init, skip_global=args.skip_global, refine=args.refine, device=args.device,
-                        descriptor=args.descriptor)
+                        descriptor=args.descriptor, source_colors=colors[0], target_colors=colors[1])
     if args.out:
         np.savetxt(args.out, res["T"], fmt="%.17g")
     print(json.dumps(dict(fitness=res["fitness"], rmse=res["rmse"], iterations=res["iterations"], n_corr=res["n_corr"],

@@ -918,6 +918,32 @@ size_t imf_icp_plane_workspace_bytes(int64_t n_src, int64_t n_dst);
 int imf_icp_point_to_plane(const double *src, int64_t n_src, const double *dst, const double *dst_normals, int64_t n_dst,
                            double max_corr_dist, const double *init_host, int max_iteration, double *out_T,
                            double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+/* imf_color_gradient.  Replaces: nothing upstream; the per-point colour gradient Open3D's registration_colored_icp
+ * (TransformationEstimationForColoredICP; Park, Zhou, Koltun, ICCV 2017) prepares for its target, restated -- the rule, and
+ * that it is recalled rather than checked, is stated in csrc/colored_icp.hip.  The entry does not search: neighbors int32
+ * [n,knn] and counts int32 [n] are the lists imf_estimate_normals wrote for the same points (the point itself included,
+ * padded with -1; entries outside [0, n) are skipped).  points, normals: device fp64 [n,3]; intensity: device fp64 [n];
+ * 1 <= n < 2^30; 1 <= knn <= 64.  Output (device): out_grad fp64 [n,3], the least-squares gradient of the intensity in the
+ * tangent plane of every point, 0 where the list has fewer than 4 entries or the 3x3 system is singular (a pivot <= 1e-12
+ * times the largest diagonal entry).  fp64 without fused multiply-add, butterfly sums over the list positions, no
+ * floating-point atomics: bit-identical from run to run.  1 launch, no workspace, no host synchronisation. */
+int imf_color_gradient(const double *points, const double *normals, const double *intensity, const int32_t *neighbors,
+                       const int32_t *counts, int64_t n, int knn, double *out_grad, void *stream);
+/* imf_icp_colored.  Replaces: Open3D registration_colored_icp(src, dst, max_corr_dist, init,
+ * TransformationEstimationForColoredICP(lambda_geometric), ICPConvergenceCriteria(max_iteration)) (nothing upstream calls
+ * it; it is `--refine color` of imfnet_amd/register.py and reconstruct.py).  Everything of imf_icp_point_to_plane holds
+ * -- the loop, the correspondence rule, fitness, rmse over point distances, the stop rule, the outputs, the launches, the
+ * LDL^T solve and its singular rule, bit-identical runs -- except the sums of the update, which are those of
+ * lambda J_G^T J_G + (1 - lambda) J_I^T J_I and lambda J_G r_G + (1 - lambda) J_I r_I (csrc/colored_icp.hip).
+ * src_intensity: device fp64 [n_src], row i the intensity of src row i; dst_normals, dst_gradient: device fp64 [n_dst,3],
+ * dst_intensity: device fp64 [n_dst], row j belonging to dst row j (dst_gradient: imf_color_gradient's output).
+ * 0 <= lambda_geometric <= 1; 1 forms point-to-plane's sums exactly.  workspace: imf_icp_colored_workspace_bytes,
+ * 256-byte aligned. */
+size_t imf_icp_colored_workspace_bytes(int64_t n_src, int64_t n_dst);
+int imf_icp_colored(const double *src, const double *src_intensity, int64_t n_src, const double *dst,
+                    const double *dst_normals, const double *dst_intensity, const double *dst_gradient, int64_t n_dst,
+                    double max_corr_dist, double lambda_geometric, const double *init_host, int max_iteration, double *out_T,
+                    double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
 /* imf_estimate_normals.  Replaces: o3d.geometry.PointCloud.estimate_normals with its default KDTreeSearchParamKNN(knn=30)
  * (data/fuse_fragments_3DMatch.py:89), exactly (the rules are stated in csrc/normals.hip).  points: device fp64 [n,3];
  * 1 <= knn <= 64; max_radius finite and > 0: the neighbour set of point i is the knn smallest of (d^2, index) among the
