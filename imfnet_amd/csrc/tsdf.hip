@@ -53,7 +53,13 @@
 // (behind the camera, beyond depth_trunc + sdf_trunc, outside one of the four side planes) into an LDS bit mask: a
 // frame whose bit is clear would have been skipped by every voxel of the unit, so the skip changes no result.  The
 // world -> camera matrices are read with wave-uniform addresses.  No floating-point atomics and a fixed frame order:
-// two runs are bit-identical, and frames fed in several calls give the bits of one call.  extract: a count pass per
+// two runs are bit-identical, and frames fed in several calls give the bits of one call.
+// PRECONDITION of integrate: every world2cam is rigid, or holds a NaN (the frame is then skipped by every voxel).  The cull
+// measures the unit's bounding sphere in the camera's frame with the radius it has in the volume's frame, widened by a
+// relative 1e-6; that covers a rotation block whose singular values lie within 1e-6 of 1 (float32-rounded poses are at
+// about 1e-7) and nothing beyond: under a pose with scale the voxels of partly visible units are silently lost.
+// imfnet_amd/fuse.py refuses poses beyond half that margin (RIGID_TOL); a caller of the raw entry points owes the same.
+// extract: a count pass per
 // unit, one exclusive scan over the units, a write pass that repeats the count with a workgroup scan per 256 voxels,
 // so the output order is (unit, voxel = (z * 16 + y) * 16 + x, axis).  No workgroup waits for another one.
 #include "common.h"

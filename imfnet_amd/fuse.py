@@ -14,6 +14,13 @@ from . import _lib
 
 UNIT_VOXELS = 4096
 FLAG_RANGE, FLAG_CAPACITY = 1, 2
+# integrate's frustum cull (csrc/tsdf.hip: k_tsdf_integrate) bounds a unit by a sphere in the camera's frame and gives its
+# radius r0 a relative margin of 1e-6.  A voxel at q and the unit's centre c lie |M (q - c)| <= s_max |q - c| <= s_max r0 apart
+# in the camera's frame (M: world2cam's rotation block, s_max its largest singular value), so the sphere holds the unit
+# exactly when s_max <= 1 + 1e-6.  Half of the margin is accepted here, on either side of 1; the other half is left to the
+# rounding of the check itself and of the kernel's fp64 sphere tests (both orders of magnitude smaller).  Float32-rounded
+# relative poses, as the fragment command line forms them, measure about 1e-7.
+RIGID_TOL = 5e-7
 
 
 def _ptr(t):
@@ -54,12 +61,30 @@ def _color_to_device(color, device):
     return t.to(device, non_blocking=True).contiguous()
 
 
+def check_rigid(poses_cam2world, what):
+    """ValueError for the first finite pose whose world2cam rotation block has |singular value - 1| > RIGID_TOL (world2cam's
+    singular values are the reciprocals of cam2world's).  A pose that holds a NaN or an infinity stays what it was: a frame
+    to skip."""
+    P = np.asarray(poses_cam2world, np.float64)
+    finite = np.flatnonzero(np.isfinite(P).all((1, 2)))
+    if len(finite) == 0:
+        return
+    s = np.linalg.svd(P[finite, :3, :3], compute_uv=False)
+    with np.errstate(divide="ignore"):
+        err = np.abs(1.0 / s - 1.0).max(1)
+    bad = np.flatnonzero(~(err <= RIGID_TOL))
+    if len(bad):
+        raise ValueError(f"TSDFVolume.{what}: pose {finite[bad[0]]} is not rigid: a singular value of its world2cam rotation "
+                         f"block is {err[bad[0]]:.3g} away from 1 (at most {RIGID_TOL:g}; the frustum cull relies on it)")
+
+
 class TSDFVolume:
     """A sparse TSDF volume in device memory.  `allocate` opens the 16^3-voxel units around the depth samples of a batch of
     frames (any number of calls, all before the first `integrate`), `integrate` folds a batch of frames into the running
     average in frame order, `extract` returns the surface points as float64 [n,3] in a defined order, `extract_mesh` the
     surface as vertices and triangles; `voxels` / `load_voxels` save and restore the state.  Frames fed in
-    several goes give the bits of one go.  lattice_offset: 0.5 samples the voxel centres (Open3D), 0 the voxel corners
+    several goes give the bits of one go.  Poses are rigid (RIGID_TOL; a ValueError names the first frame that is not) or
+    hold a NaN, which skips the frame.  lattice_offset: 0.5 samples the voxel centres (Open3D), 0 the voxel corners
     (the lattice the published 3DMatch fragments lie on).  color=True keeps a running mean colour per voxel beside the
     tsdf: every `integrate` then takes the colour frames too, `extract(colors=True)` / `extract_mesh(colors=True)` return
     uint8 colours row for row, `colors` / `load_colors` save and restore the colour state.  The geometry of a coloured
@@ -94,7 +119,7 @@ class TSDFVolume:
             raise _lib.ImfError(f"imf_tsdf_allocate_workspace_bytes refuses unit_capacity={cap}")
         self._ws = torch.empty(ws, dtype=torch.uint8, device=dev)
 
-    def _check_frames(self, depth, poses):
+    def _check_frames(self, depth, poses, what):
         d = _depth_to_device(depth, self.device)
         P = np.asarray(poses, np.float64)
         if P.shape != (d.shape[0], 4, 4):
@@ -102,6 +127,7 @@ class TSDFVolume:
         if tuple(d.shape[1:]) != (self.params.height, self.params.width):
             raise ValueError(f"depth frames are {tuple(d.shape[1:])}, the volume expects "
                              f"({self.params.height}, {self.params.width})")
+        check_rigid(P, what)
         return d, P
 
     def _allocate_call(self, d, c2w, reset):
@@ -113,7 +139,7 @@ class TSDFVolume:
     def allocate(self, depth_u16, poses_cam2world):
         if self._voxels is not None:
             raise _lib.ImfError("TSDFVolume.allocate after integrate: the unit rows are final once frames are integrated")
-        d, P = self._check_frames(depth_u16, poses_cam2world)
+        d, P = self._check_frames(depth_u16, poses_cam2world, "allocate")
         c2w = torch.from_numpy(np.ascontiguousarray(P[:, :3, :].reshape(-1, 12))).to(self.device)
         first = not self._pending
         self._pending.append((d, c2w))
@@ -146,7 +172,7 @@ class TSDFVolume:
             raise _lib.ImfError(f"TSDFVolume.{what}: the volume keeps no colour (TSDFVolume(color=True))")
 
     def integrate(self, depth_u16, poses_cam2world, color=None):
-        d, P = self._check_frames(depth_u16, poses_cam2world)
+        d, P = self._check_frames(depth_u16, poses_cam2world, "integrate")
         if color is None and self.color:
             raise _lib.ImfError("TSDFVolume.integrate: a coloured volume integrates every frame with its colour image")
         if color is not None:

@@ -1054,7 +1054,10 @@ int imf_tsdf_allocate(const uint16_t *depth, int n_frames, const double *cam2wor
                       int reset, imf_slot *table, int64_t table_capacity, int32_t *units, int64_t unit_capacity,
                       int32_t *n_units, void *workspace, size_t workspace_bytes, void *stream);
 /* The running average of every voxel of the first min(n_units[0], max_units) units over the frames in frame order
- * (world2cam: volume -> camera).  One workgroup per unit; max_units workgroups are launched. */
+ * (world2cam: volume -> camera).  One workgroup per unit; max_units workgroups are launched.
+ * Precondition of imf_tsdf_integrate and imf_tsdf_integrate_rgb: every world2cam is rigid (the singular values of its
+ * rotation block within 1e-6 of 1; float32-rounded poses are) or holds a NaN, which skips the frame.  The frustum cull
+ * relies on it and the calls do not check it: a pose with scale silently loses voxels of partly visible units. */
 int imf_tsdf_integrate(const uint16_t *depth, int n_frames, const double *world2cam, const imf_tsdf_params *params,
                        const int32_t *units, const int32_t *n_units, int64_t max_units, float *voxels, void *stream);
 /* One point per sign change between a voxel and its +x / +y / +z neighbour, fp64 [n,3] in the order (unit, voxel, axis).

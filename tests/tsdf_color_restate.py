@@ -35,8 +35,9 @@ class _RememberingDepth:
         return self
 
 
-def integrate_rgb(units, depth, color, world2cam, K, p, state=None, fused=False):
-    """(tsdf, w, colour) after the frames in order; `state` = (tsdf, w, colour) continues an earlier call."""
+def integrate_rgb(units, depth, color, world2cam, K, p, state=None, fused=False, trace=None):
+    """(tsdf, w, colour) after the frames in order; `state` = (tsdf, w, colour) continues an earlier call; `trace` as in
+    tsdf_restate.integrate (per frame, the number of voxels updated in every unit)."""
     n = len(units)
     shape = (n, RES, RES, RES)
     if state is None:
@@ -48,7 +49,7 @@ def integrate_rgb(units, depth, color, world2cam, K, p, state=None, fused=False)
     one = np.float32(1.0)
     for f in range(depth.shape[0]):
         seen = _RememberingDepth(depth[f])
-        new_tsdf, new_w = R.integrate(units, seen, world2cam[f:f + 1], K, p, state=(tsdf, w), fused=fused)
+        new_tsdf, new_w = R.integrate(units, seen, world2cam[f:f + 1], K, p, state=(tsdf, w), fused=fused, trace=trace)
         updated = new_w != w                                  # the weight moves exactly when the tsdf is updated
         iv, iu = seen.pixel
         rgb = color[f][iv, iu].astype(np.float32)             # [n, 16, 16, 16, 3]; junk where not updated, not used

@@ -68,8 +68,29 @@ def _positions(units, p):
     return px[:, None, None, :], py[:, None, :, None], pz[:, :, None, None]
 
 
-def integrate(units, depth, world2cam, K, p, state=None, fused=False):
-    """(tsdf, weight) float32 [n, 16, 16, 16] (z, y, x) after the frames in order; `state` continues an earlier call."""
+CULL_CONDITIONS = ("front", "left", "right", "top", "bottom", "near")
+
+
+def cull_conditions(units, M, K, p, height, width):
+    """Per voxel, the outcome of each single condition that the kernel's frustum cull tests on a unit's bounding sphere,
+    for one frame with world2cam M: bool [n, 16, 16, 16] under the names of CULL_CONDITIONS =
+    z > 0, uf >= 0, uf < width, vf >= 0, vf < height, z <= depth_trunc + sdf_trunc.  The four image sides are the rule's
+    own expressions, so they mean something only where z > 0."""
+    units = np.asarray(units)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    shape = (len(units), RES, RES, RES)
+    px, py, pz = (np.broadcast_to(a, shape) for a in _positions(units, p))
+    with np.errstate(all="ignore"):
+        z = _affine(M, px, py, pz, 2, False)
+        x, y = _affine(M, px, py, pz, 0, False), _affine(M, px, py, pz, 1, False)
+        uf, vf = fx * x / z + cx + 0.5, fy * y / z + cy + 0.5
+        return dict(front=z > 0.0, left=uf >= 0.0, right=uf < float(width), top=vf >= 0.0, bottom=vf < float(height),
+                    near=z <= p["depth_trunc"] + p["sdf_trunc"])
+
+
+def integrate(units, depth, world2cam, K, p, state=None, fused=False, trace=None):
+    """(tsdf, weight) float32 [n, 16, 16, 16] (z, y, x) after the frames in order; `state` continues an earlier call.
+    `trace`: a list that gets, per frame, the number of voxels the frame updates in every unit (int64 [n])."""
     n = len(units)
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     F, H, W = depth.shape
@@ -98,6 +119,8 @@ def integrate(units, depth, world2cam, K, p, state=None, fused=False):
             avg = (tsdf * w + new) / (w + np.float32(1.0))
             tsdf = np.where(ok, avg, tsdf).astype(np.float32)
             w = np.where(ok, w + np.float32(1.0), w).astype(np.float32)
+            if trace is not None:
+                trace.append(ok.reshape(n, -1).sum(1))
     return tsdf, w
 
 
