@@ -8,6 +8,10 @@
 // key occurs among the keys of the sampled raw points.  The device version keeps the reference's
 // key (so even an FNV collision selects the same rows): sample keys go into an open-addressing set,
 // voxel keys probe it, survivors are compacted in order (count / scan / emit).
+//
+// Contract: finite coordinates.  The key follows numpy for every finite quotient, beyond the int64 range included only
+// as far as the two casts agree (|quotient| < 2^63).  A NaN coordinate is outside the contract: numpy casts NaN to
+// INT64_MIN, the device converts it to 0, so the two would select different rows.
 #include "common.h"
 
 namespace imf {

@@ -6,7 +6,8 @@
 //
 // Sampled pair s: (i_s, j_s) = pairs[pos_sel[s]], a_s = f0[i_s], b_s = f1[j_s].
 //   hard01[s] = sel1[k], k = argmin_k |a_s - f1[sel1[k]]|^2;  hard10[s] = sel0[k], k = argmin_k |b_s - f0[sel0[k]]|^2
-//               (imf_nn_search itself: fp64 scores of the fp32 rows, a tie goes to the lowest k);
+//               (imf_nn_search itself: fp64 scores of the fp32 rows, a tie goes to the lowest k; its "no neighbour"
+//               answer -1 for a non-finite row reads as k = 0 with keep = 0);
 //   keep01[s]   = 0 when (i_s, hard01[s]) is one of the n_pairs positive pairs, else 1;  keep10[s]: (hard10[s], j_s).
 //               Membership is exact: the injective key i + j * max(n0, n1) in a key-only open-addressing set
 //               (common.h hash_insert_key); integer compare-and-swap only, and a set has no order;
@@ -173,11 +174,14 @@ __global__ __launch_bounds__(256) void k_hc_terms(const float *__restrict__ f0, 
   const int64_t s_raw = gid / LP;
   const bool live = s_raw < n_pos;           // whole groups are live or not; dead groups shadow the last pair
   const int64_t s = live ? s_raw : n_pos - 1;
-  const int64_t h01 = sel1[nn01[s]], h10 = sel0[nn10[s]];
+  // imf_nn_search answers -1 for a row without a neighbour (a non-finite feature row): gather row 0 and keep the pair
+  // out of the negative term, as train/loss.py does
+  const int k01_nn = nn01[s], k10_nn = nn10[s];
+  const int64_t h01 = sel1[max(k01_nn, 0)], h10 = sel0[max(k10_nn, 0)];
   const HcTerm t = hc_term<LP>(f0, f1, pairs, pos_sel, s, h01, h10, q);
   if (!live || q != 0) return;
-  const bool k01 = !hash_contains_key(table, capmask, (uint64_t)(t.i + h01 * hash_m));
-  const bool k10 = !hash_contains_key(table, capmask, (uint64_t)(h10 + t.j * hash_m));
+  const bool k01 = k01_nn >= 0 && !hash_contains_key(table, capmask, (uint64_t)(t.i + h01 * hash_m));
+  const bool k10 = k10_nn >= 0 && !hash_contains_key(table, capmask, (uint64_t)(h10 + t.j * hash_m));
   const double r01 = fmax(neg_thresh - t.d01, 0.0), r10 = fmax(neg_thresh - t.d10, 0.0);
   hard01[s] = h01;
   hard10[s] = h10;

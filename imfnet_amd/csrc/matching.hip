@@ -5,10 +5,33 @@
 // `arange(n2) == nn12[nn21]`, the ground-truth transform of the matched frag2 keypoints and the
 // `distance < inlier_thresh` count.
 //
-// The KD-tree is exact, so the device search has to be exact too: scores are formed in fp64 on the
-// f64 matrix pipe (v_mfma_f64_16x16x4_f64) as |d|^2 - 2 q.d, the argmin over the database is kept
+// The KD-tree is exact; the device search is exact up to a stated bound.  Scores are formed in fp64 on
+// the f64 matrix pipe (v_mfma_f64_16x16x4_f64) as |d|^2 - 2 q.d, the argmin over the database is kept
 // per lane in registers (ties -> lowest index, like a first-minimum scan), database splits are
 // combined by a second small kernel.  5 000 x 5 000 x 32 is 1.6 GFLOP of fp64 per direction.
+//
+// The bound.  The products of two float32 values are exact in fp64 (48 bits), so the only rounding is
+// that of the additions: dim - 1 for the norm |d|^2 (error <= g(dim - 1) |d|^2, g(k) = k u / (1 - k u),
+// u = 2^-53), then a (dim + 1)-term accumulation of that norm and the dim terms -2 q_c d_c (error <=
+// g(dim) (|d|^2 (1 + g(dim - 1)) + 2 sum |q_c d_c|), in whatever order the matrix pipe adds the four
+// products of one instruction).  No term passes through more than 2 dim - 1 additions, so the computed
+// score s(q, d) = |d|^2 - 2 q.d differs from the exact one by at most
+//   g(2 dim - 1) (|d|^2 + 2 |q| |d|)  <=  E(q, d) = 2 (dim + 2) u (|q| + |d|)^2,
+// by Cauchy-Schwarz, |d|^2 + 2 |q| |d| <= (|q| + |d|)^2 and g(2 dim - 1) <= 2 (dim + 2) u for dim <= 64.
+// Consequences, in exact arithmetic on the float32 rows:
+//   * the row returned is within E(q, got) + E(q, argmin) of the nearest row's squared distance, and is
+//     the exact argmin wherever the best two distinct distances differ by more than the sum of their E;
+//   * bitwise equal rows get bitwise equal scores (same operations in the same order, whatever lane,
+//     block, tile or split holds them), and among them the lowest index is returned;
+//   * dist2 = max(s + |q|^2, 0) is within 2 E of the exact squared distance.
+// Overflow is outside the bound: rows whose |d|^2 is not finite in fp64 are handled by the rules below,
+// and float32 rows cannot overflow an fp64 sum of dim <= 64 squares.
+//
+// Non-finite rows.  (1) A database row with a NaN or an infinity has norm NaN (k_row_norm2), so its
+// score is NaN against every query and it is never chosen.  (2) A query that ends with no row chosen or
+// with a score that is not finite -- its own row is not finite, or no database row is -- gets nn = -1
+// and dist2 = NaN (k_nn_combine).
+// Every consumer of nn treats a negative index as "no neighbour".
 #include "common.h"
 
 namespace imf {
@@ -26,7 +49,7 @@ __global__ __launch_bounds__(256) void k_row_norm2(const float *__restrict__ x, 
   const float *r = x + i * dim;
   double s = 0.0;
   for (int c = 0; c < dim; ++c) s += (double)r[c] * (double)r[c];
-  out[i] = s;
+  out[i] = (s - s != 0.0) ? __builtin_nan("") : s;   // inf or NaN in the row: NaN scores, never chosen
 }
 
 // One wave = 16 queries (MFMA column = lane & 15) against database rows [d_begin, d_end) of split
@@ -121,11 +144,15 @@ __global__ __launch_bounds__(256) void k_nn_combine(const double *__restrict__ p
       bidx = part_idx[(int64_t)s * nq + q];
     }
   }
-  nn[q] = bidx;
+  // No row: every score was NaN or +inf (bidx never set), or the best is -inf.  Finite rows give finite scores, so
+  // either means that the query row or every database row is not finite (an infinite query scores -inf where
+  // q_c d_c > 0, and would otherwise win with it).
+  const bool none = bidx == 0x7fffffff || best - best != 0.0;
+  nn[q] = none ? -1 : bidx;
   if (dist2) {
     double qn = 0.0;
     for (int c = 0; c < dim; ++c) qn += (double)Q[(int64_t)q * dim + c] * (double)Q[(int64_t)q * dim + c];
-    dist2[q] = fmax(best + qn, 0.0);
+    dist2[q] = none ? __builtin_nan("") : fmax(best + qn, 0.0);
   }
 }
 

@@ -16,6 +16,12 @@
 // Samples are drawn with replacement: a repeated pick passes the edge-length checker (0 against 0) and its fit is rank
 // deficient; registration.h's rank rule makes that fit a proper rotation all the same (rank 0: a pure translation).
 //
+// A correspondence with corres[i] < 0 or corres[i] >= n_dst is "no correspondence" (imf_nn_search writes -1 for a
+// query without a neighbour): a hypothesis that draws one fails the checkers without its points being loaded and is not
+// counted in meta[2]; scoring reads row 0 in its place and masks the result, so it is never an inlier.  The draws are
+// unchanged (r % n_src) and fitness keeps n_src as its denominator, as Open3D's fitness is over source points.  dst is
+// never read outside [0, n_dst).
+//
 // On the GPU the 50 000 hypotheses are independent: one thread fits and checks each (fp64, 3x3
 // one-sided Jacobi SVD), one wavefront scores each surviving hypothesis over all correspondences, one
 // workgroup picks the winner in a fixed order.
@@ -37,19 +43,24 @@ __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
 // one thread per hypothesis: sample, fit, checkers; valid[it] = 1 and Ts[it] = [R|t] when it survives
 __global__ __launch_bounds__(256) void k_ransac_hypotheses(const double *__restrict__ src, const double *__restrict__ dst,
                                                            const int32_t *__restrict__ corres, int n_corres,
-                                                           int ransac_n, double max_dist, double edge_sim,
+                                                           int n_dst, int ransac_n, double max_dist, double edge_sim,
                                                            uint64_t seed, int max_iter, double *__restrict__ Ts,
                                                            uint8_t *__restrict__ valid) {
   const int it = blockIdx.x * blockDim.x + threadIdx.x;
   if (it >= max_iter) return;
   V3 s[kMaxSample], d[kMaxSample];
+  bool ok = true;
   for (int j = 0; j < ransac_n; ++j) {
     const uint64_t r = splitmix64(seed ^ ((uint64_t)it * kMaxSample + j));
     const int ci = (int)(r % (uint64_t)n_corres);
+    const int cj = corres[ci];
+    if (cj < 0 || cj >= n_dst) {                  // no correspondence: the hypothesis fails, nothing is loaded
+      ok = false;
+      break;
+    }
     s[j] = load3(src, ci);
-    d[j] = load3(dst, corres[ci]);
+    d[j] = load3(dst, cj);
   }
-  bool ok = true;
   for (int i = 0; i < ransac_n && ok; ++i)      // CorrespondenceCheckerBasedOnEdgeLength
     for (int j = i + 1; j < ransac_n; ++j) {
       const V3 es = sub(s[i], s[j]), ed = sub(d[i], d[j]);
@@ -74,8 +85,8 @@ __global__ __launch_bounds__(256) void k_ransac_hypotheses(const double *__restr
 
 // one wavefront per hypothesis: inlier count and squared error over all correspondences
 __global__ __launch_bounds__(256) void k_ransac_score(const double *__restrict__ src, const double *__restrict__ dst,
-                                                      const int32_t *__restrict__ corres, int n_corres, double max_dist,
-                                                      int max_iter, const double *__restrict__ Ts,
+                                                      const int32_t *__restrict__ corres, int n_corres, int n_dst,
+                                                      double max_dist, int max_iter, const double *__restrict__ Ts,
                                                       const uint8_t *__restrict__ valid, int32_t *__restrict__ inliers,
                                                       double *__restrict__ err2) {
   const int it = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -92,9 +103,11 @@ __global__ __launch_bounds__(256) void k_ransac_score(const double *__restrict__
   int cnt = 0;
   double e2 = 0.0;
   for (int i = lane; i < n_corres; i += 64) {
-    const V3 e = sub(apply(T, load3(src, i)), load3(dst, corres[i]));
+    const int ci = corres[i];
+    const bool has = (unsigned)ci < (unsigned)n_dst;   // no correspondence: row 0 is read in its place, never an inlier
+    const V3 e = sub(apply(T, load3(src, i)), load3(dst, has ? ci : 0));
     const double dis = sqrt(dot(e, e));
-    if (dis < max_dist) {
+    if (has && dis < max_dist) {
       ++cnt;
       e2 += dis * dis;
     }
@@ -201,8 +214,8 @@ int imf_ransac_registration(const double *src, int64_t n_src, const double *dst,
                             void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   IMF_REQUIRE(src && dst && corres && out_T && out_meta && out_stats && workspace, "imf_ransac_registration: null pointer");
-  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30), "imf_ransac_registration: n_src=%lld n_dst=%lld",
-              (long long)n_src, (long long)n_dst);
+  IMF_REQUIRE(n_src >= 1 && n_dst >= 1 && n_src < (1ll << 30) && n_dst <= 0x7fffffffll,
+              "imf_ransac_registration: n_src=%lld n_dst=%lld", (long long)n_src, (long long)n_dst);
   IMF_REQUIRE(ransac_n >= 3 && ransac_n <= kMaxSample, "imf_ransac_registration: ransac_n=%d (3 or 4)", ransac_n);
   IMF_REQUIRE(max_iter >= 1 && max_iter <= (1 << 24), "imf_ransac_registration: max_iter=%d", max_iter);
   IMF_REQUIRE(workspace_bytes >= imf_ransac_workspace_bytes(max_iter), "imf_ransac_registration: workspace %zu < %zu",
@@ -211,11 +224,11 @@ int imf_ransac_registration(const double *src, int64_t n_src, const double *dst,
   double *err2 = Ts + (size_t)max_iter * 12;
   int32_t *inl = (int32_t *)(err2 + max_iter);
   uint8_t *valid = (uint8_t *)(inl + max_iter);
-  k_ransac_hypotheses<<<(unsigned)div_up(max_iter, 256), 256, 0, stream>>>(src, dst, corres, (int)n_src, ransac_n,
-                                                                         max_corr_dist, edge_similarity, seed, max_iter,
+  k_ransac_hypotheses<<<(unsigned)div_up(max_iter, 256), 256, 0, stream>>>(src, dst, corres, (int)n_src, (int)n_dst,
+                                                                         ransac_n, max_corr_dist, edge_similarity, seed, max_iter,
                                                                          Ts, valid);
-  k_ransac_score<<<(unsigned)div_up(max_iter, 4), 256, 0, stream>>>(src, dst, corres, (int)n_src, max_corr_dist, max_iter,
-                                                                    Ts, valid, inl, err2);
+  k_ransac_score<<<(unsigned)div_up(max_iter, 4), 256, 0, stream>>>(src, dst, corres, (int)n_src, (int)n_dst, max_corr_dist,
+                                                                    max_iter, Ts, valid, inl, err2);
   k_ransac_select<<<1, 1024, 0, stream>>>(inl, err2, max_iter, Ts, (int)n_src, out_T, out_meta, out_stats);
   IMF_CHECK_LAUNCH("imf_ransac_registration");
   return IMF_OK;

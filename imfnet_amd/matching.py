@@ -25,7 +25,9 @@ def _descs(x, device, name):
 
 
 def nn_search(query, db, return_dist2=False):
-    """Device tensors in, device tensors out: nn int32 [n_query] (and squared fp64 distances)."""
+    """Device tensors in, device tensors out: nn int32 [n_query] (and squared fp64 distances).  A db row with a NaN or
+    an infinity is never chosen; a query left without a row (its own row is not finite, or no db row is) gets nn = -1 and
+    dist2 = NaN.  Mask nn >= 0 before gathering with it: -1 would wrap to the last row."""
     if query.shape[1] != db.shape[1]:
         raise ImfError(f"descriptor widths differ: {query.shape[1]} vs {db.shape[1]}")
     if db.shape[0] == 0:
@@ -100,7 +102,8 @@ def feature_match(frag1_kpts, frag1_descs, frag2_kpts, frag2_descs, gt_pose, inl
     """The FMR part of `register_fragment_pair` (scripts/evaluation_3dmatch.py:207-234): both
     nearest-neighbour searches, the mutual check, the ground-truth transform and the inlier count.
     Returns (num_inliers, inlier_ratio, frag2_match_indices, frag21_nnindices); inlier_ratio is nan
-    when there is no mutual match (the reference divides 0 by 0)."""
+    when there is no mutual match (the reference divides 0 by 0).  frag21_nnindices holds -1 where `nn_search` found
+    no neighbour (a non-finite descriptor row); such a keypoint is never a mutual match."""
     d1 = _descs(frag1_descs, device, "frag1_descs")
     d2 = _descs(frag2_descs, device, "frag2_descs")
     nn21 = nn_search(d2, d1)
@@ -113,7 +116,8 @@ def feature_match(frag1_kpts, frag1_descs, frag2_kpts, frag2_descs, gt_pose, inl
 def ransac_registration(src, dst, corres, ransac_n=3, max_corr_dist=0.075, edge_similarity=0.9, max_iter=50000,
                         seed=0, device="cuda"):
     """Device RANSAC on given correspondences (imf_ransac_registration).  Returns (T 4x4 numpy
-    source->target, winning iteration, inliers, hypotheses that passed the checkers, fitness, rmse)."""
+    source->target, winning iteration, inliers, hypotheses that passed the checkers, fitness, rmse).  corres[i] < 0 or
+    >= len(dst) means "no correspondence" (`nn_search`'s -1): never drawn into a surviving hypothesis, never an inlier."""
     s = torch.as_tensor(src).to(device=device, dtype=torch.float64).contiguous()
     d = torch.as_tensor(dst).to(device=device, dtype=torch.float64).contiguous()
     c = torch.as_tensor(corres).to(device=s.device, dtype=torch.int32).contiguous()

@@ -85,13 +85,17 @@ def hardest_contrastive_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_sample
 
     d01 = nn_search(posF0.detach().float().contiguous(), subF1.detach().float().contiguous()).long()
     d10 = nn_search(posF1.detach().float().contiguous(), subF0.detach().float().contiguous()).long()
+    # nn_search answers -1 for a row without a neighbour (a non-finite feature row): gather row 0 instead of wrapping to
+    # the last row, and leave the pair out of the negative term
+    has01, has10 = d01 >= 0, d10 >= 0
+    d01, d10 = d01.clamp_min(0), d10.clamp_min(0)
     D01min = torch.sqrt((posF0 - subF1[d01]).pow(2).sum(1) + 1e-7)
     D10min = torch.sqrt((posF1 - subF0[d10]).pow(2).sum(1) + 1e-7)
 
     pos_keys = hash_keys(pairs[:, 0], pairs[:, 1], hash_seed)
     D01ind, D10ind = s1[d01], s0[d10]
-    mask0 = ~torch.isin(hash_keys(pos_ind0, D01ind, hash_seed), pos_keys)
-    mask1 = ~torch.isin(hash_keys(D10ind, pos_ind1, hash_seed), pos_keys)
+    mask0 = ~torch.isin(hash_keys(pos_ind0, D01ind, hash_seed), pos_keys) & has01
+    mask1 = ~torch.isin(hash_keys(D10ind, pos_ind1, hash_seed), pos_keys) & has10
     pos_loss = F_.relu((posF0 - posF1).pow(2).sum(1) - pos_thresh)
     neg_loss0 = F_.relu(neg_thresh - D01min[mask0]).pow(2)
     neg_loss1 = F_.relu(neg_thresh - D10min[mask1]).pow(2)

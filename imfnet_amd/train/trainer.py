@@ -359,15 +359,16 @@ class HardestContrastiveTrainer:
                 i0 = torch.as_tensor(rng.choice(len(F0), min(len(F0), 5000), replace=False)).to(dev)
                 i1 = torch.as_tensor(rng.choice(len(F1), min(len(F1), 5000), replace=False)).to(dev)
                 nn = nn_search(F0[i0].contiguous(), F1[i1].contiguous()).long()
-                x0, x1 = xyz0[i0], xyz1[i1[nn]]
+                x0, x1 = xyz0[i0], xyz1[i1[nn.clamp_min(0)]]
             else:
                 nn = nn_search(F0.contiguous(), F1.contiguous()).long()
-                x0, x1 = xyz0, xyz1[nn]
+                x0, x1 = xyz0, xyz1[nn.clamp_min(0)]
+            found = nn >= 0        # nn_search: -1 = no neighbour (a non-finite feature row); row 0 stands in, never a hit
             T = torch.as_tensor(it["trans"], dtype=torch.float64, device=dev)
             raw = robust_transform_device(x0.contiguous(), x1.contiguous())
             x0 = x0 @ T[:3, :3].t() + T[:3, 3]
             dist = torch.sqrt(((x0 - x1) ** 2).sum(1) + 1e-6)
-            hr_dev = (dist < c.hit_ratio_thresh).double().mean()
+            hr_dev = ((dist < c.hit_ratio_thresh) & found).double().mean()
             T_est = raw[:128].view(torch.float64).reshape(4, 4)
             d = (xyz0 @ T_est[:3, :3].t() + T_est[:3, 3]) - (xyz0 @ T[:3, :3].t() + T[:3, 3])
             loss = torch.clamp(torch.sqrt((d ** 2).sum(1)), max=1.0).mean()        # corr_dist, lib/metrics.py:13-19

@@ -840,8 +840,16 @@ void imf_graph_destroy(void *graph_exec);
  * imf_nn_search replaces util/uio.py:245-258 `knn_search(points_src, points_dst, k=1)` (one Open3D
  * KD-tree query per row, fp64) as called twice at scripts/evaluation_3dmatch.py:207-210: for every
  * row of `query` [n_query, dim] the index of the row of `db` [n_db, dim] with the smallest squared L2
- * distance.  Exact: scores are formed in fp64 (f64 matrix pipe); ties go to the lowest index.
- * dim in {16, 32, 64}.  nn_dist2 (optional, may be null) receives the squared distance in fp64.
+ * distance.  Scores |d|^2 - 2 q.d are formed in fp64 (f64 matrix pipe) from exact products, so each is
+ * within E(q, d) = 2 (dim + 2) 2^-53 (|q| + |d|)^2 of its exact value (derived in csrc/matching.hip): the
+ * row returned is within E(q, got) + E(q, argmin) of the nearest squared distance, and is the exact argmin
+ * wherever the best two distinct distances differ by more than the sum of their E.  Bitwise equal rows
+ * score bitwise equally; ties go to the lowest index.
+ * dim in {16, 32, 64}.  nn_dist2 (optional, may be null) receives the squared distance in fp64, within
+ * 2 E of the exact value.
+ * Non-finite rows: a db row holding a NaN or an infinity is never chosen, whatever the query; a query
+ * that is left without a row (its own row is not finite, or no db row is) gets nn_index = -1 and
+ * nn_dist2 = NaN.  Consumers treat a negative index as "no neighbour".
  * workspace: imf_nn_workspace_bytes(n_query, n_db) bytes of device memory. */
 size_t imf_nn_workspace_bytes(int64_t n_query, int64_t n_db);
 int imf_nn_search(const float *query, int64_t n_query, const float *db, int64_t n_db, int dim,
@@ -874,7 +882,10 @@ int imf_select_keypoints(const double *samples, int64_t n_samples, const double 
  * registration_ransac_based_on_feature_matching(..., TransformationEstimationPointToPoint(False),
  * ransac_n, [EdgeLength(edge_similarity), Distance(max_corr_dist)], RANSACConvergenceCriteria(max_iter,
  * 1000), mutual_filter=False) given the correspondences corres[i] = nearest target feature of source
- * point i (imf_nn_search(src_feat, dst_feat)).  src [n_src,3], dst [n_dst,3] device fp64.  All
+ * point i (imf_nn_search(src_feat, dst_feat)).  src [n_src,3], dst [n_dst,3] device fp64.  An entry
+ * corres[i] < 0 or >= n_dst is "no correspondence": a hypothesis that draws one fails the checkers (it is
+ * not counted in out_meta[2]), the entry is never an inlier, dst is never read outside [0, n_dst); the
+ * draws (r % n_src) and the fitness denominator n_src are unaffected.  All
  * max_iter hypotheses are drawn (the reference's second criterion never fires); the draw sequence is a
  * counter-based generator of `seed` (Open3D's clock-seeded one cannot be reproduced), identical in
  * the oracle.  out_T: device 16 doubles, row-major 4x4 source->target (identity if nothing survives);

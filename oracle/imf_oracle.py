@@ -518,7 +518,9 @@ def seeded_state_dict(seed=0, conv1_kernel_size=5, in_channels=1, out_channels=3
 # ---------------------------------------------------------------------------------------------
 def knn_search(points_src, points_dst, k=1, chunk=256):
     """util/uio.py:245-258: exact nearest row of points_dst for every row of points_src, fp64
-    `sum((a-b)^2)` distances; on exact ties the lowest index (first minimum)."""
+    `sum((a-b)^2)` distances; on exact ties the lowest index (first minimum).  Defined for finite rows only: the
+    device's rules for a NaN or an infinity (imf_nn_search: such a db row is never chosen, a query left without a row
+    gets -1) are restated in tests/matching_cases.py, not here."""
     assert k == 1
     src = np.asarray(points_src, dtype=np.float64)
     dst = np.asarray(points_dst, dtype=np.float64)
@@ -670,15 +672,19 @@ def ransac_registration(src, dst, corres, ransac_n=3, max_corr_dist=0.075, edge_
                         max_iter=50000, seed=0):
     """scripts/benchmark_util.py:16-34 with the correspondences given (corres[i] = nearest target
     feature of source point i).  Returns (T 4x4 source->target, winning iteration or -1, inlier count,
-    hypotheses that passed the checkers, fitness, inlier_rmse)."""
+    hypotheses that passed the checkers, fitness, inlier_rmse).  An entry corres[i] < 0 or >= len(dst) is "no
+    correspondence": a hypothesis that draws one fails the checkers, the entry is never an inlier; the draws and the
+    fitness denominator len(src) are unaffected."""
     src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
-    corres = np.asarray(corres)
+    corres = np.asarray(corres).astype(np.int64)
+    has = (corres >= 0) & (corres < len(dst))
+    corres = np.where(has, corres, 0)                                     # row 0 stands in; `has` masks every use
     n = len(src)
     it = np.arange(max_iter, dtype=np.uint64)
     picks = np.stack([(_splitmix64(np.uint64(seed) ^ (it * np.uint64(4) + np.uint64(j))) % np.uint64(n)).astype(np.int64)
                       for j in range(ransac_n)], 1)                       # [iter, ransac_n]
     S, D = src[picks], dst[corres[picks]]
-    ok = np.ones(max_iter, bool)
+    ok = has[picks].all(1)
     for i in range(ransac_n):                                             # CorrespondenceCheckerBasedOnEdgeLength
         for j in range(i + 1, ransac_n):
             ds = np.linalg.norm(S[:, i] - S[:, j], axis=1)
@@ -691,7 +697,7 @@ def ransac_registration(src, dst, corres, ransac_n=3, max_corr_dist=0.075, edge_
     tgt = dst[corres]
     for h in np.flatnonzero(ok):                                          # ascending: ties keep the earliest
         dis = np.linalg.norm(src @ T[h, :3, :3].T + T[h, :3, 3] - tgt, axis=1)
-        inl = dis < max_corr_dist
+        inl = (dis < max_corr_dist) & has
         c = int(inl.sum())
         if c == 0:
             continue
