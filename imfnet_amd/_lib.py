@@ -291,6 +291,11 @@ SIGNATURES = {
     "imf_color_gradient": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P]),
     "imf_icp_colored_workspace_bytes": (_Z, [_L, _L]),
     "imf_icp_colored": (_I, [_P, _P, _L, _P, _P, _P, _P, _L, _D, _D, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "imf_rgbd_frame_bytes": (_Z, [_I, _I, _I]),
+    "imf_rgbd_prepare": (_I, [_P, _P, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I, _P, _Z, _P]),
+    "imf_rgbd_odometry_workspace_bytes": (_Z, [_I, _I, _I]),
+    "imf_rgbd_odometry": (_I, [_P, _P, _P, C.POINTER(C.c_int), _I, _D, _D, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "imf_rgbd_odometry_stage": (_I, [_P, _P, _I, _P, _D, _D, _P, _P, _P, _Z, _P]),
     "imf_normals_workspace_bytes": (_Z, [_L]),
     "imf_estimate_normals": (_I, [_P, _L, _I, _D, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "imf_fpfh_workspace_bytes": (_Z, [_L, _I]),

@@ -198,35 +198,6 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_corr(Grid g, const double *
   }
 }
 
-// x of A x = -b for the symmetric 6x6 A by LDL^T without pivoting; false under the singular rule of the file header
-__device__ bool solve_plane_system(const double A[6][6], const double b[6], double x[6]) {
-  double L[6][6], D[6], big = 0.0;
-  for (int k = 0; k < 6; ++k) big = fmax(big, A[k][k]);
-  for (int j = 0; j < 6; ++j) {
-    double d = A[j][j];
-    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
-    if (!(d > 1e-12 * big)) return false;               // zero, negative, tiny or NaN
-    D[j] = d;
-    for (int i = j + 1; i < 6; ++i) {
-      double s = A[i][j];
-      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k] * D[k];
-      L[i][j] = s / d;
-    }
-  }
-  double y[6];
-  for (int i = 0; i < 6; ++i) {                          // L y = -b
-    double s = -b[i];
-    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-    y[i] = s;
-  }
-  for (int i = 5; i >= 0; --i) {                         // L^T x = D^-1 y
-    double s = y[i] / D[i];
-    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * x[k];
-    x[i] = s;
-  }
-  return true;
-}
-
 // one workgroup per stage; kPlane selects the sums' layout and the update (point-to-point: Umeyama, point-to-plane: LDL^T)
 template <bool kPlane>
 __global__ __launch_bounds__(kFitThreads) void k_icp_fit(const double *__restrict__ partial, int n_blocks, int64_t n_src,
@@ -271,12 +242,7 @@ __global__ __launch_bounds__(kFitThreads) void k_icp_fit(const double *__restric
       for (int a = 0; a < 6; ++a)
         for (int c = a; c < 6; ++c) A[a][c] = A[c][a] = sums[k++];
       for (int a = 0; a < 6; ++a) b[a] = sums[23 + a];
-      if (n_corr > 0 && solve_plane_system(A, b, x)) {
-        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-        U[0] = cg * cb; U[1] = cg * sb * sa - sg * ca; U[2] = cg * sb * ca + sg * sa;  U[3] = x[3];   // Rz Ry Rx
-        U[4] = sg * cb; U[5] = sg * sb * sa + cg * ca; U[6] = sg * sb * ca - cg * sa;  U[7] = x[4];
-        U[8] = -sb;     U[9] = cb * sa;                U[10] = cb * ca;                U[11] = x[5];
-      }
+      if (n_corr > 0 && solve_plane_system(A, b, x)) update_from_solution(x, U);   // both in registration.h
     } else if (n_corr > 0) {
       const double inv = 1.0 / cnt;
       const V3 ms{sums[2] * inv, sums[3] * inv, sums[4] * inv}, md{sums[5] * inv, sums[6] * inv, sums[7] * inv};

@@ -139,4 +139,43 @@ __host__ __device__ inline V3 apply(const double *T, V3 p) {
           T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]};
 }
 
+// x of A x = -b for the symmetric 6x6 A by LDL^T without pivoting; false under the singular rule of icp.hip's header: a
+// pivot <= 1e-12 times the largest diagonal entry, or NaN.  Shared by the point-to-plane / coloured ICP fit (icp.hip) and
+// the RGB-D odometry fit (odometry.hip).
+__device__ inline bool solve_plane_system(const double A[6][6], const double b[6], double x[6]) {
+  double L[6][6], D[6], big = 0.0;
+  for (int k = 0; k < 6; ++k) big = fmax(big, A[k][k]);
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
+    if (!(d > 1e-12 * big)) return false;               // zero, negative, tiny or NaN
+    D[j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k] * D[k];
+      L[i][j] = s / d;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {                          // L y = -b
+    double s = -b[i];
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s;
+  }
+  for (int i = 5; i >= 0; --i) {                         // L^T x = D^-1 y
+    double s = y[i] / D[i];
+    for (int k = i + 1; k < 6; ++k) s -= L[k][i] * x[k];
+    x[i] = s;
+  }
+  return true;
+}
+
+// The update of that solution, row-major 3x4: [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5]
+__device__ inline void update_from_solution(const double x[6], double U[12]) {
+  const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+  U[0] = cg * cb; U[1] = cg * sb * sa - sg * ca; U[2] = cg * sb * ca + sg * sa;  U[3] = x[3];   // Rz Ry Rx
+  U[4] = sg * cb; U[5] = sg * sb * sa + cg * ca; U[6] = sg * sb * ca - cg * sa;  U[7] = x[4];
+  U[8] = -sb;     U[9] = cb * sa;                U[10] = cb * ca;                U[11] = x[5];
+}
+
 }  // namespace imf

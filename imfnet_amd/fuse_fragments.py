@@ -22,6 +22,14 @@ cloud_bin_K.mesh.ply (with --color: with vertex colours); cloud_bin_K.ply keeps 
 --threads sizes the decode pool (upstream: joblib workers); the next fragment's depth (and, under --color, colour) files
 are decoded while the GPU works on the current one.  Without --color every file has the bytes it had before the flag
 existed.
+--poses odometry is for a sequence without .pose.txt files (one somebody recorded themselves): no pose file is read, every
+frame's colour file is decoded, and the fragment's camera poses come from frame-to-frame RGB-D odometry on the GPU
+(imfnet_amd/odometry.py `track`; --odometry_levels, --odometry_max_depth_diff, --odometry_depth_max).  A frame
+the odometry loses is left out as a frame with a NaN pose is (the fragment's first frame is the reference and always
+kept, so every fragment is written); cloud_bin_K.pose.npy is the float32 identity (the fragment
+lives in its own first camera, what reconstruct expects of unposed fragments) and cloud_bin_K.frames.pkl gains "poses":
+float64 [F,4,4] of the kept frames relative to the fragment's first, which integrate_scene uses in place of the pose files.
+With --poses file (the default) every output byte is what it was before the option existed.
 """
 import argparse
 import concurrent.futures as cf
@@ -137,9 +145,37 @@ def select_frames(color_paths, sid, eid, read_pose=read_extrinsic):
     return base, frames
 
 
+def load_unposed_fragment(cfg, color_paths, sid, eid, pool):
+    """--poses odometry: every frame's depth and colour, no pose file read; `poses` is None until `run` has tracked them."""
+    stems = [color_paths[fid][:-10] for fid in range(sid, eid)]
+    color = pool.map(lambda s: read_color_jpg(s + ".color.jpg", cfg.height, cfg.width), stems)
+    depth = list(pool.map(lambda s: read_depth_png(s + ".depth.png", cfg.height, cfg.width), stems))
+    return dict(base=np.eye(4, dtype=np.float32), stems=stems, depth=np.stack(depth), color=np.stack(list(color)), poses=None)
+
+
+def gpu_track(cfg, intrinsic, frag):
+    """(poses cam2first float64 [F,4,4], kept bool [F]) of an unposed fragment's frames (imfnet_amd.odometry.track)."""
+    from .odometry import track
+    levels = cfg.odometry_levels
+    iterations = tuple(5 * 2 ** k for k in range(levels))[::-1]          # 5 at level 0, doubling per level: (20, 10, 5) for 3
+    return track(frag["depth"], frag["color"], intrinsic[:3, :3], levels=levels, iterations=iterations,
+                 max_depth_diff=cfg.odometry_max_depth_diff, depth_scale=cfg.depth_scale, depth_max=cfg.odometry_depth_max,
+                 device=cfg.device)
+
+
+def apply_track(frag, poses, kept):
+    """Leaves out the frames the odometry dropped, exactly as select_frames leaves out NaN poses."""
+    keep = np.flatnonzero(kept)
+    frag["stems"] = [frag["stems"][i] for i in keep]
+    frag["depth"], frag["color"] = frag["depth"][keep], frag["color"][keep]
+    frag["poses"] = frag["tracked"] = np.ascontiguousarray(poses[keep], np.float64)
+
+
 def load_fragment(cfg, color_paths, sid, eid, pool):
     """Poses and decoded depth of one fragment (under --color: `color` uint8 [F,H,W,3] of the same frames too), or None when
     it writes nothing."""
+    if getattr(cfg, "poses", "file") == "odometry":
+        return load_unposed_fragment(cfg, color_paths, sid, eid, pool)
     base, frames = select_frames(color_paths, sid, eid)
     if base is None:
         return None
@@ -243,7 +279,10 @@ def write_fragment(cfg, out_folder, frag_id, frag, xyz, normals=None, mesh=None,
         write_ply_normals(os.path.join(out_folder, f"cloud_bin_{frag_id}.ply"), xyz, normals, rgb)
     np.save(os.path.join(out_folder, f"cloud_bin_{frag_id}.pose.npy"), frag["base"])
     with open(os.path.join(out_folder, f"cloud_bin_{frag_id}.frames.pkl"), "wb") as fh:
-        pickle.dump({"frames": frag["stems"]}, fh, protocol=pickle.HIGHEST_PROTOCOL)
+        record = {"frames": frag["stems"]}
+        if "tracked" in frag:                                # --poses odometry: what integrate_scene reads instead of .pose.txt
+            record["poses"] = frag["tracked"]
+        pickle.dump(record, fh, protocol=pickle.HIGHEST_PROTOCOL)
     if cfg.write_image and frag["stems"]:
         shutil.copyfile(frag["stems"][0] + ".color.jpg", os.path.join(out_folder, f"cloud_bin_{frag_id}_0.jpg"))
 
@@ -262,10 +301,11 @@ def gpu_fuse(cfg, intrinsic, frag):
     return (vol.extract(), vol.extract_mesh()) if getattr(cfg, "mesh", False) else vol.extract()
 
 
-def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
+def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals, track=gpu_track):
     """Walks the tree; `fuse(cfg, intrinsic, fragment) -> float64 [n,3]` (under --mesh: `(points, (vertices, triangles))`;
     under --color: dict(points, rgb, mesh = (vertices, triangles, rgb) or None)) does the volume work, `normals(cfg, xyz)`
-    the normals under --normals.  Returns the fragments written."""
+    the normals under --normals, `track(cfg, intrinsic, fragment) -> (poses, kept)` the poses under --poses odometry.
+    Returns the fragments written."""
     if cfg.voxel_length is None:
         cfg.voxel_length = cfg.tsdf_cubic_size / 512.0
     ensure_dir(cfg.out_root)
@@ -289,6 +329,8 @@ def run(cfg, fuse=gpu_fuse, log=print, normals=fragment_normals):
             if frag is None:
                 log(f"    {scene}/{seq} fragment {k}: no pose for its first frame, nothing written")
                 continue
+            if frag["poses"] is None:                        # --poses odometry
+                apply_track(frag, *track(cfg, intrinsic, frag))
             xyz = fuse(cfg, intrinsic, frag)
             rgb = None
             if isinstance(xyz, dict):
@@ -324,6 +366,11 @@ def parse_args(argv=None):
                     help="also write cloud_bin_K.mesh.ply: the triangle mesh of the same volume (marching tetrahedra)")
     ap.add_argument("--color", action="store_true",
                     help="integrate every frame's .color.jpg too: uchar red, green, blue in the PLY (and, with --mesh, in the mesh)")
+    ap.add_argument("--poses", choices=("file", "odometry"), default="file",
+                    help="file = every frame's .pose.txt (the data set's); odometry = frame-to-frame RGB-D odometry on the GPU")
+    ap.add_argument("--odometry_levels", type=int, default=3, help="pyramid levels of the odometry, 1..5; 5 stages at the finest level, twice as many at each coarser one (3: 20, 10, 5)")
+    ap.add_argument("--odometry_max_depth_diff", type=float, default=0.03, help="metres between a pixel and its match")
+    ap.add_argument("--odometry_depth_max", type=float, default=4.0, help="metres; depth beyond it is ignored by the odometry")
     ap.add_argument("--device", default="cuda")
     return ap.parse_args(argv)
 

@@ -13,7 +13,8 @@ A fragment whose X_k is not finite (no kept pair reaches it) or that the traject
 
 Frame f of fragment K gets the scene pose X_K . inv(base_K) . pose_f: base_K from cloud_bin_K.pose.npy, pose_f read as
 float32, the relative pose inv(base_K) . pose_f formed in float32 exactly as fuse_fragments.select_frames forms it, the
-product with X_K in fp64.  The frame files are found by the basenames recorded in cloud_bin_K.frames.pkl.  All fragments
+product with X_K in fp64.  A frames.pkl that holds "poses" (fuse_fragments --poses odometry) gives the relative poses
+itself, in fp64, and no .pose.txt is read.  The frame files are found by the basenames recorded in cloud_bin_K.frames.pkl.  All fragments
 are allocated first (the unit rows must be final before the first frame is integrated), then integrated fragment by
 fragment in order, at most 4096 frames per call; the next fragment is decoded while the GPU works on the current one.
 Writes SCENE/scene_mesh.ply (fuse_fragments.write_ply_mesh; TSDFVolume.extract_mesh) and prints one JSON
@@ -46,7 +47,12 @@ def scene_poses(fragments, raw_seq, k, X):
     base = np.load(os.path.join(fragments, f"cloud_bin_{k}.pose.npy"))
     base_inv = np.linalg.inv(base)
     with open(os.path.join(fragments, f"cloud_bin_{k}.frames.pkl"), "rb") as fh:
-        stems = pickle.load(fh)["frames"]
+        record = pickle.load(fh)
+    stems = record["frames"]
+    if "poses" in record:                                    # fuse_fragments --poses odometry: no pose file is read
+        rel = np.asarray(record["poses"], np.float64)
+        return [(os.path.join(raw_seq, os.path.basename(stem)), np.matmul(X, np.matmul(base_inv.astype(np.float64), T)))
+                for stem, T in zip(stems, rel)]
     out = []
     for stem in stems:
         stem = os.path.join(raw_seq, os.path.basename(stem))

@@ -955,6 +955,39 @@ int imf_icp_colored(const double *src, const double *src_intensity, int64_t n_sr
                     const double *dst_normals, const double *dst_intensity, const double *dst_gradient, int64_t n_dst,
                     double max_corr_dist, double lambda_geometric, const double *init_host, int max_iteration, double *out_T,
                     double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes, void *stream);
+/* imf_rgbd_prepare, imf_rgbd_odometry.  Replaces: nothing upstream; Open3D's compute_rgbd_odometry with the hybrid term
+ * (Steinbruecker 2011; Park, Zhou, Koltun 2017), the frame-to-frame step in front of the fragment fusion of Choi, Zhou,
+ * Koltun 2015, restated -- the rules, and that they are recalled rather than checked, are stated in csrc/odometry.hip.
+ * imf_rgbd_prepare builds the pyramids of one frame into an opaque device block of imf_rgbd_frame_bytes(h, w, levels) bytes
+ * (0 for a shape it refuses), 256-byte aligned: smoothed intensity, depth (NaN where invalid), their Sobel gradients, per
+ * level.  depth_u16: device uint16 [h,w]; color_u8: device uint8 [h,w,3]; 1 <= levels <= 5; h and w divisible by
+ * 2^(levels-1), the coarsest level at least 3 x 3; depth valid iff u16 > 0 and depth_min < u16 / depth_scale < depth_max;
+ * depth_edge > 0: the largest depth step inside a 3 x 3 neighbourhood that still has a depth gradient.  2 levels + 1 launches.
+ * imf_rgbd_odometry fits src_frame onto dst_frame (both blocks of imf_rgbd_prepare, of one shape; the two headers are read
+ * back once before anything is enqueued, after that the host never waits): iterations: HOST int[n_iterations], coarsest level
+ * first, n_iterations = the frames' levels, every count >= 1; init_host: HOST double[16] row-major or NULL = identity;
+ * 0 <= lambda_depth <= 1; a stage with fewer than min_corr correspondences has the identity update.  Outputs (device):
+ * out_T fp64 [16], source camera into target camera; out_info fp64 [36], the 6 x 6 system matrix of a last stage at level 0,
+ * exactly symmetric; out_stats fp64 [2] = fitness (correspondences / valid source pixels at level 0), cost; out_meta int32 [4]
+ * = correspondences, flags (bit 0: a stage had too few correspondences or a singular system; bit 1: the last stage had:
+ * the pair is lost), stages run (the last included), valid source pixels.  fp64 without fused multiply-add in every per-pixel
+ * quantity, fixed summation order, integer atomics only (the occlusion test): bit-identical from run to run.
+ * workspace: imf_rgbd_odometry_workspace_bytes(h, w, levels) (0 for a shape refused), 256-byte aligned.
+ * imf_rgbd_odometry_stage is the test surface: one stage at `level` with T_dev (DEVICE double[16]); out_winner int32
+ * [h_l, w_l] (the source index v w + u that won the target pixel, or -1), out_sums fp64 [29] (correspondences, cost, the 21
+ * upper entries of the system matrix row-major, the 6 of the right-hand side). */
+size_t imf_rgbd_frame_bytes(int h, int w, int levels);
+int imf_rgbd_prepare(const uint16_t *depth_u16, const uint8_t *color_u8, int h, int w, double fx, double fy, double cx,
+                     double cy, double depth_scale, double depth_min, double depth_max, double depth_edge, int levels,
+                     void *frame, size_t frame_bytes, void *stream);
+size_t imf_rgbd_odometry_workspace_bytes(int h, int w, int levels);
+int imf_rgbd_odometry(const void *src_frame, const void *dst_frame, const double *init_host, const int *iterations,
+                      int n_iterations, double max_depth_diff, double lambda_depth, int min_corr, double *out_T,
+                      double *out_info, double *out_stats, int32_t *out_meta, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int imf_rgbd_odometry_stage(const void *src_frame, const void *dst_frame, int level, const double *T_dev,
+                            double max_depth_diff, double lambda_depth, int32_t *out_winner, double *out_sums,
+                            void *workspace, size_t workspace_bytes, void *stream);
 /* imf_estimate_normals.  Replaces: o3d.geometry.PointCloud.estimate_normals with its default KDTreeSearchParamKNN(knn=30)
  * (data/fuse_fragments_3DMatch.py:89), exactly (the rules are stated in csrc/normals.hip).  points: device fp64 [n,3];
  * 1 <= knn <= 64; max_radius finite and > 0: the neighbour set of point i is the knn smallest of (d^2, index) among the
