@@ -150,7 +150,7 @@ class FragmentIO(C.Structure):
                 ("main_stream", C.c_void_p), ("side_stream", C.c_void_p), ("image_stream", C.c_void_p),
                 ("trace", C.POINTER(NetTrace)), ("levels", LevelDesc * 4), ("serialize", C.c_int32),
                 ("fp32_buffers", C.c_int32), ("head_on_side", C.c_int32), ("gpu_idle_hint", C.c_int32),
-                ("inputs_event", C.c_void_p), ("reuse_event", C.c_void_p)]
+                ("inputs_event", C.c_void_p), ("reuse_event", C.c_void_p), ("ahead_stream", C.c_void_p)]
 
 
 class TsdfParams(C.Structure):
@@ -242,6 +242,7 @@ SIGNATURES = {
                               C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _I, _I]),
     "imf_stream_create": (_P, []),
     "imf_stream_destroy": (None, [_P]),
+    "imf_streams_concurrent": (_I, [_P, _P]),
     "imf_event_create": (_P, []),
     "imf_event_destroy": (None, [_P]),
     "imf_event_record": (_I, [_P, _P]),
@@ -258,6 +259,9 @@ SIGNATURES = {
     "imf_resunet_int_arena_bytes_cap": (_Z, [C.POINTER(ResunetDesc), C.POINTER(C.c_int64), _Z]),
     "imf_resunet_float_arena_bytes_cap": (_Z, [C.POINTER(ResunetDesc), C.POINTER(C.c_int64)]),
     "imf_fragment_pyramid_bytes": (_Z, [C.POINTER(FragmentCaps)]),
+    "imf_abi_sizeof_fragment_io": (_Z, []),
+    "imf_resunet_encoder_ahead": (_I, [_I, _I]),
+    "imf_fragment_ahead_forwards": (C.c_long, []),
     "imf_fragment_forward": (_I, [C.POINTER(ResunetDesc), C.POINTER(ImageDesc), C.POINTER(FragmentCaps),
                                   C.POINTER(FragmentIO)]),
     "imf_pipeline_create": (_P, [_P, _I, _I]),

@@ -184,6 +184,7 @@ struct FragmentCtx {
   imf_fragment_io *fio;
   hipStream_t imgs;
   bool head_on_side;   // level 0 was issued on the SIDE stream (imf_fragment_io.head_on_side): the main stream joins it
+  hipStream_t ahead;   // the stream of the launches carried ahead of the main stream (imf_fragment_io.ahead_stream); null: none
 };
 
 int fork_image_branch(const FragmentCtx &c, hipStream_t main) {
@@ -203,6 +204,14 @@ int fork_image_branch(const FragmentCtx &c, hipStream_t main) {
 #endif
 constexpr int kMetaBBox = 8;                        // meta[2 * n_levels + 0..7] with n_levels = 4
 constexpr int kMetaStarts = 16;                     // meta[16 + IMF_MAX_BATCH * level + item]
+constexpr int kAheadEvent = 13;                     // ahead mode: the end of the launches on the ahead stream, which the main stream joins
+constexpr int kAheadMarkBegin = 14, kAheadMarkMain = 15;   // optional diagnostic marks (tools/ahead_timeline.py): the ahead chain's
+                                                    // begin, the main chain's begin behind the join
+constexpr int kAheadEncoder = 12, kAheadFusion = 13;   // conv1 + the encoder's 11 convolutions; ... and the fusion
+#ifndef IMF_ENCODER_AHEAD_DEFAULT
+#define IMF_ENCODER_AHEAD_DEFAULT kAheadEncoder     // measured: LAB_NOTES 4i
+#endif
+thread_local long g_ahead_forwards = 0;             // forwards the CALLING thread issued in ahead mode (imf_fragment_ahead_forwards)
 
 /* ---- imf_resunet_forward in pieces.  The ORDER -- what is issued on which stream, after what -- is in imf_resunet_forward
    itself, at the end; the pieces below issue their own launches and nothing else. ---- */
@@ -218,6 +227,12 @@ struct Forward {
   const int32_t *meta;
   int32_t *err;                    // flag word: capacity mode collects every flag in the level-0 error word; exact mode takes the caller's (optional)
   hipStream_t main, side, sorts;   // sorts: the stream of the occupancy sorts (issue_sorts)
+  // Ahead mode (imf_fragment_io.ahead_stream): the first n_ahead launches of the main chain -- conv1, the encoder's convolutions,
+  // the fusion as the 13th -- go to `enc`, which is not ordered behind the previous forward's decoder on `main`; the rest stays
+  // on `main`, behind ONE join (events[kAheadEvent]).  Not ahead: enc == main, n_ahead == 0 -- one chain, as ever.
+  hipStream_t enc;
+  int n_ahead;
+  hipStream_t chain_stream(int launch) const { return launch < n_ahead ? enc : main; }
   bool first_and_map;              // conv1 + the level-0 map in one launch (fragment forward; measured against two launches on two streams in round 3)
   Forward(const imf_resunet_desc *net, const imf_resunet_io *io);
 };
@@ -272,6 +287,11 @@ Forward::Forward(const imf_resunet_desc *net_, const imf_resunet_io *io_) : net(
   // sorts at the end of the SIDE chain the head of step k + 1 queued behind 240 us of sorts and the steps lost what the twins
   // gain).  Otherwise: the side stream, at the end of its chain.
   sorts = pyr && fctx->imgs && fctx->imgs != side && fctx->imgs != main ? fctx->imgs : side;
+  enc = main; n_ahead = 0;
+  if (pyr && fctx->ahead && fctx->head_on_side && s.small_first) {
+    n_ahead = imf_resunet_encoder_ahead(net->conv[19].variant, io->n_items);
+    if (n_ahead > 0) enc = fctx->ahead;
+  }
 }
 
 int build_map(const Forward &f, Rb &rb, int lin, int lout, int ksize, hipStream_t st) {
@@ -390,8 +410,8 @@ struct Formats {
   bool wants_split(int id) const { return presplit && id >= 0 && id != ebuf(3, 2) && id != HEAD; }
 };
 
-// ---- first convolution (Cin <= 4): occupancy bit grid for the all-ones feature, else hash probing; on the main stream --
-int first_convolution(const Forward &f, const Layout &l, Formats &fmt) {
+// ---- first convolution (Cin <= 4): occupancy bit grid for the all-ones feature, else hash probing; first of the main chain --
+int first_convolution(const Forward &f, const Layout &l, Formats &fmt, hipStream_t st) {
   const imf_resunet_desc *net = f.net; const imf_resunet_io *io = f.io;
   const imf_level &l0 = io->level[0]; const Sizes &s = f.s; const int32_t *meta = f.meta;
   float *out = l.buf[ebuf(0, 0)];
@@ -416,11 +436,11 @@ int first_convolution(const Forward &f, const Layout &l, Formats &fmt) {
     a.grid_filled = true; a.w_image = net->first_kernel_image;
   }
   if (f.dyn || a.grid_words) {
-    rc = conv_first_bitgrid(a, f.main);
+    rc = conv_first_bitgrid(a, st);
   } else {
     rc = imf_conv_first_fused(l0.table, l0.capacity, l0.coords, s.n[0], 1, net->first_ksize,
                               io->x_all_ones ? nullptr : io->x, net->in_channels, net->first_kernel, s.ch[1],
-                              net->first_scale, net->first_shift, 0, out, f.main);
+                              net->first_scale, net->first_shift, 0, out, st);
     wrote_split = false;   // (the hash-probing first layer writes fp32)
   }
   if (rc) return rc;
@@ -429,18 +449,18 @@ int first_convolution(const Forward &f, const Layout &l, Formats &fmt) {
 }
 
 // ---- the occupancy-sorted twins, on f.sorts (level 2 first: the decoder reaches it first) ----
-int issue_sorts(const Forward &f, Layout &l, SideChain &chain) {
+int issue_sorts(const Forward &f, Layout &l, SideChain &chain, hipStream_t after) {
   if (!(f.twin[0] || f.twin[1] || f.twin[2])) return IMF_OK;
   const imf_resunet_io *io = f.io;
   if (f.sorts != f.side) {
-    // Image stream: ONE dependency, on the MAIN stream at the point of the call (behind conv3's launch: the main stream
-    // has waited for the side chain's level-1 and level-2 maps by then, and the level-0 map is its own).  Not on the side
+    // Image stream: ONE dependency, on the main CHAIN at the point of the call (`after`: the stream that carries conv3 --
+    // behind conv3's launch it has waited for the side chain's level-1 and level-2 maps, and the level-0 map is its own).  Not on the side
     // stream's events: the side stream may have waited for the image branch (image_joined_side), and two captured streams
     // that wait for each other send hipStreamEndCapture into an endless recursion (ROCm 7.2, found with rocgdb).
-    IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[6], f.main));
+    IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[6], after));
     IMF_CHECK_HIP(hipStreamWaitEvent(f.sorts, (hipEvent_t)io->events[6], 0));
   } else if (f.twin[0] && f.first_and_map) {   // the level-0 map came out of the first convolution's launch on the MAIN stream
-    IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[6], f.main));
+    IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[6], after));
     IMF_CHECK_HIP(hipStreamWaitEvent(f.sorts, (hipEvent_t)io->events[6], 0));
   }
   for (int i = 2; i >= 0; --i) {
@@ -462,9 +482,9 @@ float *buffer_addr(const Forward &f, const Layout &l, int id) {   // Step's buff
   return id >= 0 ? l.buf[id] : id == -2 ? const_cast<float *>(f.io->x) : id == -3 ? f.io->out : nullptr;
 }
 
-// One convolution of the schedule on the main stream: the side chain's piece it waits for (lazy chain), the wait for its map,
-// imf_conv_args, the operand-format bookkeeping, the trace record.
-int launch_step(const Forward &f, const Layout &l, const Step &st, SideChain &chain, Formats &fmt) {
+// One convolution of the schedule on `stream` (the main stream, or the ahead stream for a launch carried ahead): the side
+// chain's piece it waits for (lazy chain), the wait for its map, imf_conv_args, the operand-format bookkeeping, the trace record.
+int launch_step(const Forward &f, const Layout &l, const Step &st, SideChain &chain, Formats &fmt, hipStream_t stream) {
   const imf_resunet_io *io = f.io;
   const imf_net_conv &c = f.net->conv[st.conv];
   IMF_REQUIRE(c.w_packed, "imf_resunet_forward: conv %d has no weights", st.conv);
@@ -474,7 +494,7 @@ int launch_step(const Forward &f, const Layout &l, const Step &st, SideChain &ch
   int rc;
   if ((rc = chain.ensure_for(rb))) return rc;
   if (rb.ready_event >= 0) {
-    IMF_CHECK_HIP(hipStreamWaitEvent(f.main, (hipEvent_t)io->events[rb.ready_event], 0));
+    IMF_CHECK_HIP(hipStreamWaitEvent(stream, (hipEvent_t)io->events[rb.ready_event], 0));
     rb.ready_event = -1;
   }
   imf_conv_args a;
@@ -509,11 +529,11 @@ int launch_step(const Forward &f, const Layout &l, const Step &st, SideChain &ch
     t.n_slots = rb.n_slots; t.n_out = rb.n_out; t.launched = 1;
     t.level = rb.level; t.slots_extra = rb.slots_extra; t.kernel_tag = a.kernel_tag;
   }
-  return imf_spconv_fwd(&a, f.main);
+  return imf_spconv_fwd(&a, stream);
 }
 
-// ---- bottleneck fusion (model/resunet.py:237-273), on the main stream ----
-int fusion_block(const Forward &f, const Layout &l, Formats &fmt) {
+// ---- bottleneck fusion (model/resunet.py:237-273) ----
+int fusion_block(const Forward &f, const Layout &l, Formats &fmt, hipStream_t st) {
   const imf_resunet_desc *net = f.net; const imf_resunet_io *io = f.io;
   const int fused_split = fmt.wants_split(FUSED) ? 1 : 0;   // the block's output: conv4_tr's operand image
   const int fusion_variant = (net->conv[12].variant == 6 || net->conv[12].variant == 3) ? net->conv[12].variant : 0;
@@ -521,11 +541,11 @@ int fusion_block(const Forward &f, const Layout &l, Formats &fmt) {
   if (f.dyn)
     return fusion_attention_dyn_fmt(l.buf[ebuf(3, 2)], f.s.n[3], f.meta + 6, f.meta + kMetaStarts + IMF_MAX_BATCH * 3,
                                     io->n_items, f.err, io->kt_packed, io->v_packed, io->n_tokens, io->tokens_padded,
-                                    &net->fusion, net->fusion_scale, l.buf[FUSED], l.fusion_ws, l.fusion_ws_bytes, f.main,
+                                    &net->fusion, net->fusion_scale, l.buf[FUSED], l.fusion_ws, l.fusion_ws_bytes, st,
                                     fused_split, fusion_variant);
   return fusion_attention_batched_fmt(l.buf[ebuf(3, 2)], io->n_items, io->item_row0, io->item_rows, io->kt_packed,
                                       io->v_packed, io->n_tokens, io->tokens_padded, &net->fusion, net->fusion_scale,
-                                      l.buf[FUSED], l.fusion_ws, l.fusion_ws_bytes, f.err, f.main, fused_split,
+                                      l.buf[FUSED], l.fusion_ws, l.fusion_ws_bytes, f.err, st, fused_split,
                                       fusion_variant);
 }
 
@@ -626,6 +646,22 @@ int imf_resunet_sorted_maps_n(int variant, int n_items) {
   return n_items == 1 ? (IMF_SORTED_MAPS_DEFAULT & 1) : IMF_SORTED_MAPS_DEFAULT;
 }
 
+int imf_resunet_encoder_ahead(int variant, int n_items) {
+  // How many launches of the main chain a forward with an ahead stream carries on it: 0 none (one chain, the order without an
+  // ahead stream), 1 .. 12 conv1 and the first n - 1 encoder convolutions, 13 the fusion as well.  A static function of the
+  // arithmetic and the number of fragments per forward, like imf_resunet_sorted_maps_n.  IMF_ENCODER_AHEAD (diagnostic, read
+  // once) overrides it for every forward.  The arms' figures: LAB_NOTES.md 4i.
+  // Ahead only where it was measured against one chain: bf16x3 with one, two and four fragments per forward (0.799 -> 0.662,
+  // 1.158 -> 1.019, 2.03 -> 1.90 ms).  split-f16, fp32 MFMA and eight fragments per forward keep one chain until they are measured.
+  static const int env = getenv("IMF_ENCODER_AHEAD") ? atoi(getenv("IMF_ENCODER_AHEAD")) : -1;
+  const int n = env >= 0 ? env : (variant == 3 && n_items <= 4 ? IMF_ENCODER_AHEAD_DEFAULT : 0);
+  return n > kAheadFusion ? kAheadFusion : n;
+}
+
+long imf_fragment_ahead_forwards(void) { return g_ahead_forwards; }
+
+size_t imf_abi_sizeof_fragment_io(void) { return sizeof(imf_fragment_io); }
+
 size_t imf_resunet_int_arena_bytes(const imf_resunet_desc *net, const int64_t *n, const int32_t *bbox) {
   return net && n ? exact_layout(net, n, bbox, nullptr, nullptr).int_bytes : 0;
 }
@@ -647,6 +683,8 @@ size_t imf_resunet_float_arena_bytes_cap(const imf_resunet_desc *net, const int6
 // coarse pyramid levels and every map but level 0's (SideChain); the occupancy sorts run on f.sorts (the image stream in a
 // fragment forward, else the side stream).  The main stream waits for a map right before the first launch on it
 // (Rb::ready_event), and once, in front of the fusion, for the side chain's tail and the image branch.
+// Ahead mode (Forward::enc): the first n_ahead launches of the main chain run on the AHEAD stream instead, with their waits,
+// and the main stream joins once, behind the last of them; the decoder and the head never leave the main stream.
 int imf_resunet_forward(const imf_resunet_desc *net, const imf_resunet_io *io) {
   IMF_REQUIRE(net && io, "imf_resunet_forward: null pointer");
   Layout l = io->dyn ? arena_layout(sizes_of(net, io->n), true, io->bitgrid_words, io->int_arena, io->float_arena)
@@ -660,11 +698,23 @@ int imf_resunet_forward(const imf_resunet_desc *net, const imf_resunet_io *io) {
   Formats fmt(f, sched, n_steps);
   SideChain chain(f, l);
   hipStream_t main = f.main, side = f.side;
+  // Ahead mode: launch number `launch` of the main chain (conv1 = 0, the encoder's steps, the fusion, the decoder) goes to
+  // f.chain_stream(launch).  In front of the first one that stays on the main stream, the ahead stream records its end and the
+  // main stream waits for it: from there on the main stream is behind everything this forward has issued on the ahead stream.
+  int launch = 0;
+  auto join_ahead = [&]() -> int {
+    if (f.n_ahead == 0 || launch != f.n_ahead) return IMF_OK;
+    IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[kAheadEvent], f.enc));
+    IMF_CHECK_HIP(hipStreamWaitEvent(main, (hipEvent_t)io->events[kAheadEvent], 0));
+    if (io->events[kAheadMarkMain]) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[kAheadMarkMain], main));
+    return IMF_OK;
+  };
 
   // level 0 and its maps
-  if (f.pyr && f.fctx->head_on_side) {   // level 0 was built on the side stream, ahead of the main stream: main joins here
+  if (f.pyr && f.fctx->head_on_side) {   // level 0 was built on the side stream, ahead of the main stream: the chain joins here
     IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[7], side));
-    IMF_CHECK_HIP(hipStreamWaitEvent(main, (hipEvent_t)io->events[7], 0));
+    IMF_CHECK_HIP(hipStreamWaitEvent(f.chain_stream(0), (hipEvent_t)io->events[7], 0));
+    if (f.n_ahead && io->events[kAheadMarkBegin]) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[kAheadMarkBegin], f.enc));
   } else if (f.pyr) {   // level 0 was built on the main stream: the side stream (coarse levels, rulebooks) starts after it
     IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[7], main));
     IMF_CHECK_HIP(hipStreamWaitEvent(side, (hipEvent_t)io->events[7], 0));
@@ -681,36 +731,46 @@ int imf_resunet_forward(const imf_resunet_desc *net, const imf_resunet_io *io) {
   // the side chain: everything now, or (lazy) piece by piece from launch_step
   if (!chain.lazy && (rc = chain.ensure(3, true))) return rc;
 
-  if (f.s.small_first && (rc = first_convolution(f, l, fmt))) return rc;
-  if (f.sorts == side && (rc = issue_sorts(f, l, chain))) return rc;
+  if (f.s.small_first) {
+    if ((rc = first_convolution(f, l, fmt, f.chain_stream(launch)))) return rc;
+    if (f.sorts == side && (rc = issue_sorts(f, l, chain, f.chain_stream(launch)))) return rc;
+    ++launch;
+  } else if (f.sorts == side && (rc = issue_sorts(f, l, chain, main))) return rc;
 
   // the encoder
-  for (int i = 0; i < n_enc; ++i) {
-    if ((rc = launch_step(f, l, sched[i], chain, fmt))) return rc;
-    // the sorts on the image stream: behind the launch that made the main stream wait for the level-2 map (conv3, the
+  for (int i = 0; i < n_enc; ++i, ++launch) {
+    if ((rc = join_ahead())) return rc;
+    const hipStream_t st = f.chain_stream(launch);
+    if ((rc = launch_step(f, l, sched[i], chain, fmt, st))) return rc;
+    // the sorts on the image stream: behind the launch that made the chain wait for the level-2 map (conv3, the
     // consumer of dn[1]) -- see issue_sorts
     if (f.sorts != side && sched[i].rb == &l.dn[1]) {
       if ((rc = chain.ensure(2, false))) return rc;
-      if ((rc = issue_sorts(f, l, chain))) return rc;
+      if ((rc = issue_sorts(f, l, chain, st))) return rc;
     }
   }
 
   // the fusion: behind the side chain's tail (item starts; it carries the image branch's end when image_joined_side)
-  // diagnostic marks (tools/branch_times.py hands events[11], [12] in): the main stream's arrival at the join, the fusion's end
+  // diagnostic marks (tools/branch_times.py hands events[11], [12] in): the chain's arrival at the join, the fusion's end
   if ((rc = chain.ensure(3, true))) return rc;
+  if ((rc = join_ahead())) return rc;
+  const hipStream_t fst = f.chain_stream(launch);
   const bool diag_marks = f.pyr && io->events[11] && io->events[12];
-  if (diag_marks) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[11], main));
-  if (io->image_ready && !chain.image_joined_side) IMF_CHECK_HIP(hipStreamWaitEvent(main, (hipEvent_t)io->image_ready, 0));
-  if (chain.items_event >= 0) IMF_CHECK_HIP(hipStreamWaitEvent(main, (hipEvent_t)io->events[chain.items_event], 0));
-  if ((rc = fusion_block(f, l, fmt))) return rc;
-  if (io->fusion_done) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->fusion_done, main));
-  if (diag_marks) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[12], main));
+  if (diag_marks) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[11], fst));
+  if (io->image_ready && !chain.image_joined_side) IMF_CHECK_HIP(hipStreamWaitEvent(fst, (hipEvent_t)io->image_ready, 0));
+  if (chain.items_event >= 0) IMF_CHECK_HIP(hipStreamWaitEvent(fst, (hipEvent_t)io->events[chain.items_event], 0));
+  if ((rc = fusion_block(f, l, fmt, fst))) return rc;
+  ++launch;
+  if (fst == main && io->fusion_done) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->fusion_done, main));
+  if (diag_marks) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->events[12], fst));
+  if ((rc = join_ahead())) return rc;   // (the fusion went ahead as well: the main stream joins behind it, and fusion_done with it)
+  if (fst != main && io->fusion_done) IMF_CHECK_HIP(hipEventRecord((hipEvent_t)io->fusion_done, main));
 
-  // the decoder and the head
+  // the decoder and the head: always on the main stream, which therefore carries the END of every forward
   const bool one_launch_head = head_is_fusable(f);
   const int n_tail = one_launch_head ? n_steps - 2 : n_steps;
   for (int i = n_enc; i < n_tail; ++i)
-    if ((rc = launch_step(f, l, sched[i], chain, fmt))) return rc;
+    if ((rc = launch_step(f, l, sched[i], chain, fmt, main))) return rc;
   return one_launch_head ? fused_head(f, l, fmt) : IMF_OK;
 }
 
@@ -766,7 +826,23 @@ int imf_fragment_forward(const imf_resunet_desc *net, const imf_image_desc *img,
   // its ~50 small launches (~0.2 ms as a chain) must be done by the fusion block.  Forking it later in the step -- after
   // block1 / conv2 / block2 / conv3 / block3, beside the levels that leave CUs idle -- was measured slower (1.07 ->
   // 1.15 ... 1.23 ms, round 3): the chain then ends after the encoder and the fusion waits for it.
-  FragmentCtx fctx{&pb, img, caps, fio, imgs, head_on_side};
+  // Ahead mode (imf_fragment_io.ahead_stream): with the head on the side stream, the encoder need not queue behind the
+  // previous forward's decoder either -- its launches go to the ahead stream, which takes the head's order (events[7]) and with
+  // it the caller's two dependencies; the main stream joins behind them (imf_resunet_forward).  Never for a traced step or
+  // inside a capture: those keep one chain.
+  hipStream_t ahead = nullptr;
+  if (head_on_side && fio->ahead_stream && !fio->trace) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    IMF_CHECK_HIP(hipStreamIsCapturing(main, &capturing));
+    if (capturing == hipStreamCaptureStatusNone) {
+      ahead = (hipStream_t)fio->ahead_stream;
+      IMF_REQUIRE(ahead != main && ahead != side && ahead != imgs, "imf_fragment_forward: ahead_stream must be a fourth stream");
+      IMF_REQUIRE(fio->events[kAheadEvent], "imf_fragment_forward: ahead_stream needs events[%d]", kAheadEvent);
+      if (imf_resunet_encoder_ahead(net->conv[19].variant, caps->n_items) > 0) ++g_ahead_forwards;
+      else ahead = nullptr;
+    }
+  }
+  FragmentCtx fctx{&pb, img, caps, fio, imgs, head_on_side, ahead};
   if ((rc = fork_image_branch(fctx, head))) return rc;
 
   // level 0 of the pyramid on the head's stream (conv1 needs it first); the coarse levels go to the side stream
@@ -792,6 +868,7 @@ int imf_fragment_forward(const imf_resunet_desc *net, const imf_image_desc *img,
   io.out = fio->out;
   for (int i = 0; i < 9; ++i) io.events[i] = fio->events[i];
   io.events[11] = fio->events[11]; io.events[12] = fio->events[12];   // optional diagnostic marks
+  for (int i = kAheadEvent; i <= kAheadMarkMain; ++i) io.events[i] = fio->events[i];   // the ahead join and its optional marks
   io.side_stream = side; io.main_stream = main;
   io.trace = fio->trace;
   io.fp32_buffers = fio->fp32_buffers;

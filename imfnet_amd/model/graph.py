@@ -184,7 +184,9 @@ class _Bucket:
         self.iarena = u8(L.imf_resunet_int_arena_bytes_cap(C.byref(net), rows_c, grid_words))
         self.farena = u8(L.imf_resunet_float_arena_bytes_cap(C.byref(net), rows_c))
         self.out = self.outbuf[lay["F"]:lay["F"] + rows[0] * net.out_channels * 4].view(torch.float32).view(rows[0], net.out_channels)
-        self.events = [L.imf_event_create() for _ in range(13)]   # [11], [12]: diagnostic marks around the fusion (runner.diag_events)
+        # [11], [12]: diagnostic marks around the fusion; [13]: the ahead stream's join (imf_fragment_io.ahead_stream); [14], [15]:
+        # diagnostic marks of the ahead / main chains' begins (runner.diag_events: tools/branch_times.py, tools/ahead_timeline.py)
+        self.events = [L.imf_event_create() for _ in range(16)]
         io = self.io = FragmentIO()
         io.xyz, io.xyz_is_f64, io.voxel_size = self.xyz.data_ptr(), int(is_f64), float(voxel)
         io.dyn, io.image, io.meta = self.dyn.data_ptr(), self.image.data_ptr(), self.meta.data_ptr()
@@ -195,8 +197,10 @@ class _Bucket:
         io.float_arena, io.float_arena_bytes = self.farena.data_ptr(), self.farena.numel()
         io.out = self.out.data_ptr()
         for i, e in enumerate(self.events):
-            io.events[i] = e if i < 11 or runner.diag_events else None
+            io.events[i] = e if i < 11 or i == 13 or runner.diag_events else None
         io.side_stream, io.image_stream = runner.raw_streams(dev)
+        self.ahead_stream = runner.ahead_stream(dev)   # handed in per call, with head_on_side (enqueue, FragmentStreamer.submit)
+        io.ahead_stream = None
         io.trace = None
         io.fp32_buffers = fp32_buffers()
         self.graph = C.c_void_p()
@@ -222,11 +226,17 @@ class _Bucket:
         self.io.trace = trace
         # (the streaming pipeline shares these buckets and sets head_on_side per job: a plain direct launch inherits the
         # main stream's order instead -- the bucket's previous forward may still be running on it)
-        self.io.head_on_side, self.io.inputs_event, self.io.reuse_event = 0, None, None
+        self.io.head_on_side, self.io.inputs_event, self.io.reuse_event, self.io.ahead_stream = 0, None, None, None
         if reuse_event is not None:
+            # ... and its encoder to the ahead stream, beside that decoder (imf_fragment_io.ahead_stream)
             self.io.head_on_side, self.io.reuse_event = 1, C.c_void_p(reuse_event.cuda_event)
+            self.io.ahead_stream = self.ahead_stream
+        ahead0 = self.L.imf_fragment_ahead_forwards()
         check(self.L.imf_fragment_forward(C.byref(runner.net_desc), C.byref(runner.img_plan.desc), C.byref(self.caps),
                                           C.byref(self.io)), "imf_fragment_forward")
+        # (the library counts per calling thread: the pipeline's worker, issuing beside us, does not move this difference)
+        self.last_ahead = self.L.imf_fragment_ahead_forwards() != ahead0   # this call issued launches on the ahead stream
+        runner.stats["ahead"] += int(self.last_ahead)
 
     def capture(self, runner, stream):
         L = self.L
@@ -294,12 +304,13 @@ class FragmentRunner:
         self.buckets = {}
         self._main = {}
         self._raw = {}
+        self._ahead = {}
         self._streamers = {}
         # hipGraph replay is opt-in: ROCm 7.2 runs a graph's independent branches back to back (measured 1.77 vs
         # 1.37 ms per fragment pair), the eager capacity-mode call keeps the three streams concurrent
         self.use_graph = bool(os.environ.get("IMFNET_FRAGMENT_GRAPH"))
         self.diag_events = bool(os.environ.get("IMFNET_DIAG_EVENTS"))   # tools/branch_times.py: two extra marks per step
-        self.stats = dict(graph=0, eager=0, redone=0, captured=0)
+        self.stats = dict(graph=0, eager=0, redone=0, captured=0, ahead=0)   # ahead: direct launches with the encoder on the ahead stream
         self.host_slots = []          # pinned staging of the synchronous host-array path (extract.py)
         self.stream_state = None      # streams + pinned slots of extract_features_stream
         self.cli_slots = None         # pinned slots of generate_desc's pipelined loop
@@ -352,6 +363,16 @@ class FragmentRunner:
             self._main[dev] = views[0]
             s = self._raw[dev] = (raw[1], raw[2])
         return s
+
+    def ahead_stream(self, dev):
+        """The device's ahead stream (hipStream_t) or None: the next forward's encoder runs on it beside the main stream's
+        decoder when forwards are issued back to back (imf_fragment_io.ahead_stream).  ops.ahead_stream picks it by measurement
+        behind the other three -- a stream that shares one of their hardware queues would serialise the forwards."""
+        if dev not in self._ahead:
+            from .. import ops
+            self.raw_streams(dev)
+            self._ahead[dev] = ops.ahead_stream(dev)
+        return self._ahead[dev]
 
     def streamer(self, dev, **kw):
         """The device's FragmentStreamer (stream.py): pinned host blocks in, pinned host blocks out, transfers overlapped."""

@@ -131,7 +131,8 @@ def aux_streams(device):
     right after the other.  HIP multiplexes streams onto four hardware queues (a new stream goes to the least-used one),
     and torch's pool hands its streams out in an order the process's history decides: branches that should overlap then
     share a queue and run one after the other (round 3: the same forward 0.75 or 2.0 ms, the fp32 exact-mode pair 2.3 or
-    3.4 ms).  Streams born together sit on different queues.  Every executor takes its auxiliary streams from here:
+    3.4 ms).  These three, born together, have sat on different queues in every process measured; a FOURTH born right behind
+    them has not (LAB_NOTES 4i) -- see `ahead_stream`.  Every executor takes its auxiliary streams from here:
         capacity mode (model/graph.py, stream.py):  main, side (coarse levels + rulebooks), image branch
         exact mode (extract.py, model/plan.py):      geometry, side (rulebooks), image branch
     -- the two modes never run at the same time, and the caller's own stream is the fourth."""
@@ -147,6 +148,58 @@ def aux_streams(device):
             raise ImfError("could not create the package's three streams")
         s = _AUX_STREAMS[device] = (raw, tuple(torch.cuda.ExternalStream(r, device=device) for r in raw))
     return s
+
+
+AHEAD_CANDIDATES = 6
+_AHEAD_STREAMS = {}
+AHEAD_NOTES = {}          # device -> what `ahead_stream` found there (one line)
+
+
+def ahead_stream(device):
+    """The device's AHEAD stream (raw hipStream_t) for capacity-mode forwards issued back to back
+    (imf_fragment_io.ahead_stream: the next forward's encoder beside this one's decoder), or None.  Created on first use, so
+    exact-mode callers never pay for it.  It must run BESIDE main, side and image: on a hardware queue one of them uses the
+    same issue order is 15 % slower than one chain, on another queue 12 % faster, and which queue a new stream gets depends on
+    what the process created before (LAB_NOTES 4i: the stream born right behind the three shared the image stream's queue,
+    the third or fourth after them did not).  So it is MEASURED (imf_streams_concurrent, ~1 ms per candidate, once per
+    device): the first of AHEAD_CANDIDATES new streams that runs beside all three is kept, the others are destroyed; with
+    none, None -- every forward then keeps its one main chain, and a warning says so (AHEAD_NOTES has the line).  HIP has
+    four queues and the process's default stream holds one: the queue found is usually that one, so a client that keeps
+    torch's DEFAULT stream busy while forwards run shares it with the ahead stream; such a client sets IMF_ENCODER_AHEAD=0."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device in _AHEAD_STREAMS:
+        return _AHEAD_STREAMS[device]
+    raw = aux_streams(device)[0]
+    L = _lib.lib()
+    made, found = [], None
+    with torch.cuda.device(device):
+        for _ in range(AHEAD_CANDIDATES):
+            s = L.imf_stream_create()
+            if not s:
+                break
+            made.append(s)
+            answers = [L.imf_streams_concurrent(o, s) for o in raw]
+            if min(answers) < 0:                      # the probe itself failed: an error, not "shares a queue"
+                for m in made:
+                    L.imf_stream_destroy(m)
+                raise ImfError("imf_streams_concurrent: " + L.imf_last_error().decode())
+            if all(a == 1 for a in answers):
+                found = s
+                break
+        for m in made:
+            if m != found:
+                L.imf_stream_destroy(m)
+    if found:
+        AHEAD_NOTES[device] = "ahead stream: candidate %d of %d runs beside main, side and image" % (len(made), AHEAD_CANDIDATES)
+    else:
+        AHEAD_NOTES[device] = ("no ahead stream: none of %d new streams runs beside main, side and image on %s; forwards keep "
+                               "one main chain" % (len(made), device))
+        import logging
+        logging.getLogger("imfnet_amd").warning(AHEAD_NOTES[device])
+    _AHEAD_STREAMS[device] = found
+    return found
 
 
 def geometry_stream(device):

@@ -257,6 +257,9 @@ class FragmentStreamer:
         job.defer_download = 1 if more_follow else 0
         b.io.trace = None
         b.io.head_on_side = 1 if self.head_on_side else 0
+        # one main chain: the pipeline puts its uploads and downloads into the idle halves of the image and side streams
+        # (pipeline.hip), and a job's encoder on the ahead stream (imf_fragment_io.ahead_stream) has not been measured beside them
+        b.io.ahead_stream = None
         ticket = self.L.imf_pipeline_submit(self.handle, C.byref(job))
         if ticket < 0:
             with self._lock:

@@ -773,9 +773,32 @@ typedef struct imf_fragment_io {       /* [host]; all buffers device memory owne
    * ~0.1 ms of host time earlier.  With work queued ahead (a stream of forwards) leave it 0.  imf_pipeline_* sets it per job. */
   int32_t gpu_idle_hint;
   void *inputs_event, *reuse_event;
+  /* Encoder on a fourth stream (a STREAM of forwards over several buckets; needs head_on_side).  NULL: one main chain, exactly
+   * the order described above.  A stream distinct from the other three and on a hardware queue of its own (imf_streams_concurrent): conv1 and the encoder's convolutions -- the first
+   * imf_resunet_encoder_ahead() launches of the main chain -- are issued on it behind the head (events[7]) instead of on
+   * main_stream, so forward k+1's encoder runs beside forward k's decoder: each chain fills the gaps between the other's
+   * dependent launches and the CUs its coarse levels leave idle (same kernels in the same per-forward order on the same buffers:
+   * same results).  The ahead stream takes the head's two dependencies (inputs_event, reuse_event) through events[7]; it records
+   * events[13] (required with this field) behind its last launch, and main_stream waits for that event in front of its own first
+   * launch.  The decoder and the head stay on main_stream, which therefore still carries the END of every forward: work enqueued
+   * on main_stream behind the call sees finished descriptors, and an event recorded there is a valid reuse_event as before.
+   * Everything the ahead launches touch belongs to the bucket, so reuse_event / imf_pipeline_wait's contract
+   * cover it.  Ignored -- one chain -- with head_on_side == 0, serialize, a trace, or inside a hipGraph capture.  Optional
+   * diagnostic marks: events[14] (the ahead chain may begin), events[15] (the main chain has joined). */
+  void *ahead_stream;
 } imf_fragment_io;
 
 size_t imf_fragment_pyramid_bytes(const imf_fragment_caps *caps);
+size_t imf_abi_sizeof_fragment_io(void);               /* sizeof(imf_fragment_io) as the library was built: binding checks */
+/* Launches of the main chain that a forward with an ahead_stream carries on it: 0 none, 1 .. 12 conv1 and the first n - 1 encoder
+ * convolutions, 13 the fusion too (a static function of the arithmetic and the fragments per forward: 12 for bf16x3 with up to
+ * four fragments, where it was measured, else 0; IMF_ENCODER_AHEAD overrides). */
+int imf_resunet_encoder_ahead(int variant, int n_items);
+long imf_fragment_ahead_forwards(void);                /* forwards the CALLING THREAD has issued with launches on an ahead stream */
+/* 1: a launch on stream b runs beside work on stream a (they sit on different hardware queues), 0: it waits behind it -- MEASURED
+ * (~0.7 ms, synchronises both streams).  For choosing an ahead_stream: one that shares a queue with main_stream, side_stream or
+ * image_stream serialises the forward instead of overlapping it. */
+int imf_streams_concurrent(void *a, void *b);
 int imf_fragment_forward(const imf_resunet_desc *net /* [host] */, const imf_image_desc *img /* [host] */,
                          const imf_fragment_caps *caps, imf_fragment_io *io);
 
